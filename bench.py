@@ -10,11 +10,16 @@ GPU each, RCCL) and exits with their status.  Only rank 0 prints.
 
 One step = one forward of B clips per GPU (weak scaling: per-GPU batch fixed;
 the batch shards across ranks with no collective on the data path).  Prints ONE
-JSON line on rank 0 (see DESIGN.md "Measurement").  Besides the headline
-(res15, f16x2: the fastest mode that meets the 1e-4 logit bar on res15) the line
-carries the other res15 precision modes and the
-BASELINE.json configs C2 (cnn-trad-pool2 fp32 + bf16x3), C3 (res8 bf16) and C5
-(res26-narrow training, DP over RCCL), each with its roofline.
+JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run measures only
+the headline (res15, f16x2: the fastest mode that meets the 1e-4 logit bar on
+res15): set-up, warm-up, the timed steps, the result line.  ``--full`` adds
+everything else to the line: the sample parity against the float64 oracle, the
+f16x2 admission report on the range fixtures, the other res15 precision modes,
+the BASELINE.json configs C2 (cnn-trad-pool2 fp32 + bf16x3), C3 (res8 bf16) and
+C5 (res26-narrow training, DP over RCCL), each with its roofline, and the CPU
+baseline.  ``--dump-outputs DIR`` writes what the last timed step returned
+(DIR/logits.npy, float32; DIR/loss.npy under --train) so that two builds can be
+compared output for output: the inputs are seeded and identical from run to run.
 """
 import argparse
 import json
@@ -74,10 +79,18 @@ def parse(argv=None):
                         "fp16 hi/lo weights, 2 fp16 MFMA products; 1e-4 parity on res15), bf16x3 (fp32 values as "
                         "bf16 hi/lo pairs, 3 bf16 MFMA products, fp32 accumulation; 1e-4 parity), f32 (fp32 MFMA; "
                         "1e-4 parity) or bf16 (res only; top-1 parity)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: sample parity against the float64 oracle, the f16x2 admission report, "
+                        "the other precision modes, C2, C3, C5 and the CPU baseline (trimmed by --no-alt, "
+                        "--no-configs, --no-cpu-baseline); without it only the headline is measured")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last of them returned as DIR/<name>.npy (float32; "
+                        "logits, or loss under --train; a fixed seeded sample of rows past 64 MB)")
     p.add_argument("--no-alt", action="store_true",
-                   help="skip the extra measurements (other precision modes, C2, C3, C5)")
+                   help="with --full: skip the extra measurements (other precision modes, C2, C3, C5)")
     p.add_argument("--no-configs", action="store_true",
-                   help="skip C2/C3/C5 (keep the other res precision modes): the rocprof passes of tools/profile.sh")
+                   help="with --full: skip C2/C3/C5 (keep the other res precision modes): the rocprof passes of "
+                        "tools/profile.sh")
     p.add_argument("--e2e", action="store_true",
                    help="serving pipeline: int16-scaled PCM [B,16000] in HBM -> GPU MFCC -> model -> logits")
     p.add_argument("--train", action="store_true",
@@ -453,6 +466,25 @@ def _sample_parity(model, cfg, x, out, orc, B):
             "sample_clips": len(idx)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: what the last timed step returned, as DIR/<name>.npy in float32
+    (DIR/<name>_rank<r>.npy per rank when world > 1).  The whole dump stays within
+    DUMP_MAX_BYTES: an array past its share is cut to a fixed, seeded sample of its
+    rows (in index order)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, world * len(arrays))
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().to(torch.float32).cpu().numpy())
+        if a.nbytes > share and a.ndim >= 1 and len(a) > 1:
+            keep = max(1, share // max(1, a.nbytes // len(a)))
+            idx = np.sort(np.random.Generator(np.random.PCG64(2024)).choice(len(a), size=keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def modes_summary(res, model):
     """Every measured mode and config as {value, dtype, frac}: printed as the line's last
     key, so a driver that keeps only the tail of stdout still sees every number."""
@@ -586,7 +618,7 @@ def train_flops_per_clip(cfg):
     return 3 * fwd - conv0
 
 
-def measure_train(ctx, args, name="res26-narrow", B=None):
+def measure_train(ctx, args, name="res26-narrow", B=None, dump=None):
     """C5: res26-narrow train step per rank (fwd+bwd on device, flat-bucket all-reduce
     over RCCL when world > 1, fused SGD).  Roofline: algorithmic training FLOP per
     step / step time vs the fp32 peak (the native training convs are fp32)."""
@@ -645,6 +677,8 @@ def measure_train(ctx, args, name="res26-narrow", B=None):
     t1 = time.perf_counter()
     ctx.barrier()
     reducer.remove()  # no gradient hooks outlive the timed steps
+    if dump:
+        dump_outputs(dump, {"loss": loss.detach().reshape(1)}, ctx.rank, ctx.world)
     per = hd.gather_scalar(t1 - t0, device=ctx.dev)
     el = max(per)
     fl = train_flops_per_clip(cfg)
@@ -702,7 +736,8 @@ def rank_main(args):
     ctx = Ctx(dev, rank, world, dist)
 
     if args.train:
-        res = measure_train(ctx, args, args.model if args.model != "res15" else "res26-narrow", args.batch)
+        res = measure_train(ctx, args, args.model if args.model != "res15" else "res26-narrow", args.batch,
+                            dump=args.dump_outputs)
         if rank == 0:
             res.update({"n_gpus": world, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True,
                         "scaling": "weak", "vs_baseline": None,
@@ -733,29 +768,34 @@ def rank_main(args):
         def step_fn(p):
             return model(ap.compute_mfccs_batch(p))
         el, per, out, (kms, nlaunch, kflop) = ctx.timed(step_fn, pcm, args.steps, args.warmup)
-        idx = list(range(0, B, max(1, B // 32)))[:32]
-        xs = ap.compute_mfccs_batch(pcm[idx])
-        ref = orc.forward({k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}, cfg,
-                          xs.cpu().numpy())
-        got = out[idx].cpu().numpy()
-        parity = {"top1_agreement_vs_oracle": float(np.mean(ref.argmax(1) == got.argmax(1))),
-                  "max_abs_logit_err_vs_oracle_f64": float(np.abs(ref - got).max()), "sample_clips": len(idx)}
+        parity = None
+        if args.full:
+            idx = list(range(0, B, max(1, B // 32)))[:32]
+            xs = ap.compute_mfccs_batch(pcm[idx])
+            ref = orc.forward({k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}, cfg,
+                              xs.cpu().numpy())
+            got = out[idx].cpu().numpy()
+            parity = {"top1_agreement_vs_oracle": float(np.mean(ref.argmax(1) == got.argmax(1))),
+                      "max_abs_logit_err_vs_oracle_f64": float(np.abs(ref - got).max()), "sample_clips": len(idx)}
     else:
         with torch.no_grad():
             model(x[:8])   # resolve the precision request (the policy's one-off probe) before any timing
         el, per, out, (kms, nlaunch, kflop) = ctx.timed(model, x, args.steps, args.warmup)
-        parity = _sample_parity(model, cfg, x, out, orc, B)
+        parity = _sample_parity(model, cfg, x, out, orc, B) if args.full else None
     prec = model.honk_last_precision   # the mode the request resolved to (the policy's choice)
     rerun = getattr(model, "honk_last_rerun", 0) if is_res else 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": out}, rank, world)
 
     alts = {}
-    if not args.no_alt and not args.e2e:
+    extras = args.full and not args.no_alt and not args.e2e   # a plain run: the headline alone
+    if extras:
         if is_res:
             for other in ("bf16x3", "f16x2", "f32", "bf16"):
                 if other != prec:
                     log(f"res {other} mode")
                     alts[f"{other}_mode"] = measure_res(ctx, args, args.model, other, B, x=x, model=model)
-    if not args.no_alt and not args.e2e and not args.no_configs:
+    if extras and not args.no_configs:
         del x
         torch.cuda.empty_cache()
         log("C2 cnn-trad-pool2")
@@ -786,7 +826,7 @@ def rank_main(args):
                 "frac": round(ach / MODE_PEAK[prec], 4) if ach else None, "traffic": None,
                 "launches": nlaunch, "avg_launch_ms": round(avg_ms, 4), "flop_per_launch": kflop / max(nlaunch, 1)}
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         log("cpu baseline")
         cpu = cpu_baseline(cfg, args.cpu_seconds)
     if rank == 0:
@@ -814,14 +854,15 @@ def rank_main(args):
             "per_rank_clips_s": [round(B * args.steps / t, 1) for t in per],
             "model_tflops": round(value * flop_clip / 1e12, 2),
             "roofline": roof,
-            "parity": parity,
         }
+        if parity is not None:
+            res["parity"] = parity
         if is_res:
             res["f16x2_admission"] = {"rerun_clips_last_step": rerun, "z_max": 8,
                                       "what": "every f16x2 batch is admitted per clip (tail_sum_kernel's flag, "
                                               "flag_compact_kernel, one host sync per call); flagged clips "
                                               "re-run in bf16x3 -- inside the timed steps"}
-            if args.model == "res15" and not args.e2e:
+            if args.full and args.model == "res15" and not args.e2e:
                 try:
                     res["f16x2_admission"]["fixtures"] = admission_report(dev)
                 except Exception as e:  # a report, not the measurement
