@@ -44,6 +44,13 @@
 #ifndef HONK_PAIR_MIX
 #define HONK_PAIR_MIX 1
 #endif
+// DTOP: A's k-steps 0 and 1 of a step in one scheduling region with the head of the step's
+// block (see run_mtile; 0: every k-step fenced, the head's scalar work ahead of the first
+// MFMA, measured 1 % slower).  res_vf.hip, the unit that compiles the pair and last-layer
+// kernels, turns it on.
+#ifndef HONK_PAIR_DTOP
+#define HONK_PAIR_DTOP 0
+#endif
 
 struct Block16PArgs {
   __bf16* R;            // [n][H][W][CP*SP] pre-BN x_{i-1}: A's input and B's residual; B's output in place
@@ -455,9 +462,18 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
     }
   };
   auto floordiv = [](int x, int y) { return x >= 0 ? x / y : -((y - 1 - x) / y); };
-  auto tread = [&](WalkT& k) {
+  // (role A reads the three row bases only, 12 bytes: it stores nothing to HBM, and a dead
+  // fourth element's register was reused at once -- the compiler then drained the LDS queue,
+  // the prefetched operand reads ahead of this one included, right behind this read)
+  typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
+  auto tread = [&](auto rolec, WalkT& k) {
     const char* e = lds + tbl + (k.r & (TR - 1)) * TEB;
-    k.e = *(const u32x4*)e;
+    if constexpr (decltype(rolec)::value) {
+      k.e = *(const u32x4*)e;
+    } else {
+      const u32x3 e3 = *(const u32x3*)e;
+      k.e = u32x4{e3[0], e3[1], e3[2], 0xF0000000u};
+    }
     k.lo = *(const int*)(e + 16);
     k.wb = __mul24(k.w, PXB) + g16;
     if constexpr (!PADC) {
@@ -465,16 +481,16 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
       k.okr = k.w + sc < W;
     }
   };
-  auto walk_init_t = [&](int q0) {
+  auto walk_init_t = [&](auto rolec, int q0) {
     WalkT k;
     k.r = floordiv(q0, W);
     k.w = q0 - k.r * W;
-    tread(k);
+    tread(rolec, k);
     return k;
   };
   // (rows of >= 11 pixels: the instantiated row pitches; WIDE: >= 33)
   constexpr int NWRAP = WIDE ? 1 : 3;
-  auto walk_adv_t = [&](WalkT& k) {
+  auto walk_adv_t = [&](auto rolec, WalkT& k) {
     k.w += 32;
 #pragma unroll
     for (int i = 0; i < NWRAP; ++i) {
@@ -482,7 +498,7 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
       k.w = wrap ? k.w - W : k.w;
       k.r += wrap ? 1 : 0;
     }
-    tread(k);
+    tread(rolec, k);
   };
   // per-tap constants: column offset and the tq bias (see lastc)
   int tk[9];
@@ -763,22 +779,34 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
   // The slot holds the row at the padded pitch PXB: lane l of part t fills slot
   // chunk 64 t + l, i.e. pixel (64 t + l) / (PXB / 16), 16-B chunk (64 t + l) %
   // (PXB / 16) of the HBM row, or zeros (a pad chunk, or past the row).
+  // The cursor carries the row's byte offset in the chunk, (c0 + clip) clip_bytes + (c + j d) RB,
+  // and its slot's byte offset in the ring, both advanced by additions as the lane walk's
+  // rowb / sR are (dRB within a class, dcls(n) at a class change, dclip at a clip change): no
+  // integer multiplies per step.
   struct RowCur {
-    int cl, c, j, n, slot;
+    int c, j, n;
+    unsigned off;
+    int slot;
   };
-  auto cur_adv = [&](RowCur& r) {
-    r.slot = r.slot + 1 == a.NRA ? 0 : r.slot + 1;
-    if (++r.j == r.n) {
-      r.j = 0;
-      if (++r.c == d) {
-        r.c = 0;
-        ++r.cl;
-      }
-      r.n = r.c < rem ? q1 : qd;
-    }
-  };
-  auto cur_off = [&](const RowCur& r) {  // byte offset of the row in the chunk
-    return (unsigned)(c0 + r.cl) * clip_bytes + (unsigned)((r.c + (r.j << lgd)) * RB);
+  const int ringAb = a.NRA * a.slotb;
+  // advance by one row where `by` is 1, not at all where it is 0 -- straight-line, the wrap
+  // conditions folded into the increments as in walk_adv (j < n, c < d and slot < ringAb hold
+  // on entry, so no wrap fires without the advance)
+  auto cur_adv = [&](RowCur& r, int by) {
+    const int s1 = r.slot + (by ? a.slotb : 0);
+    r.slot = s1 == ringAb ? 0 : s1;
+    const int j1 = r.j + by;
+    const bool wj = j1 == r.n;   // next class
+    const int c1 = r.c + (wj ? 1 : 0);
+    const bool wc = c1 == d;     // next clip
+    unsigned inc = by ? dRB : 0u;
+    const unsigned dcls = dclsd + (r.n == q1 ? dcls1d : 0u);
+    inc = wj ? dcls : inc;
+    inc = wc ? dclip : inc;
+    r.off += inc;
+    r.j = wj ? 0 : j1;
+    r.c = wc ? 0 : c1;
+    r.n = r.c < rem ? q1 : qd;
   };
   // per part: the lane's byte offset in the HBM row (16-bit, 0xffff: zeros)
   unsigned psrc[(PPR + 1) / 2];
@@ -806,19 +834,47 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
   const int PW = P / W, PR = P - PW * W;
   int frow = (P + 31) / W, fcol = (P + 31) - ((P + 31) / W) * W;  // k = -1
   auto frontier = [&]() { return frow + 1 < rows_total - 1 ? frow + 1 : rows_total - 1; };
-  RowCur rc{0, 0, 0, rem > 0 ? q1 : qd, 0};  // the next row to load (row 0)
-  // LM: the walk restarts at each clip
+  RowCur rc{0, 0, rem > 0 ? q1 : qd, (unsigned)c0 * clip_bytes, 0};  // the next row to load (row 0)
+  // LM: the walk restarts at each clip (run_role's prologue then derives the clip's first
+  // descriptors from the reset cursor)
   auto restart = [&]() {
     rows_total = (c1 - c0) * H;
     total = rows_total * W;
     frow = (P + 31) / W;
     fcol = (P + 31) - ((P + 31) / W) * W;
-    rc = RowCur{0, 0, 0, rem > 0 ? q1 : qd, 0};
+    rc = RowCur{0, 0, rem > 0 ? q1 : qd, (unsigned)c0 * clip_bytes, 0};
     plo = dummy;
     ppix = 0xF0000000u;
   };
+  // The step's DMA descriptors: nnew rows (F(k-1), F(k)], row m at chunk offset roff[m] into
+  // ring offset rslot[m] (entries m >= nnew are not used: their pieces go to the sink).  They
+  // are software-pipelined: step k + 1's are derived during step k (step 0's in run_role's
+  // prologue), straight-line and without multiplies, so no step waits for its own.
+  int fprev = 0, nnew = 0;
   unsigned roff[MAXR];
   int rslot[MAXR];
+  static_assert(MAXR + 2 < KSA, "desc_row(m) rides on k-step 2 + m");
+  // (The arithmetic depends on nothing but loop-carried scalars, so where it lands in the
+  // step's block is instruction selection's choice, whatever k-step calls it: the head of the
+  // block, ahead of k-step 0's first sched_barrier.  Being a step ahead it is needed nowhere
+  // in this step, so DTOP opens k-steps 0 and 1 to it and the scheduler spreads it under their
+  // MFMAs.  Pinning it to the second m-tile's k-steps with empty asm statements on the state
+  // was tried: the statements pushed the first m-tile's MFMAs behind them -- not kept.)
+  auto desc_front = [&]() {  // the frontier of the next step and its count of new rows
+    fcol += PR;
+    frow += PW;
+    const bool wrap = fcol >= W;
+    fcol -= wrap ? W : 0;
+    frow += wrap ? 1 : 0;
+    const int fcur = frontier();
+    nnew = fcur - fprev;
+    fprev = fcur;
+  };
+  auto desc_row = [&](int m) {  // row m of the next step; the cursor ends nnew (<= MAXR) rows on
+    roff[m] = rc.off;
+    rslot[m] = rc.slot;
+    cur_adv(rc, m < nnew ? 1 : 0);
+  };
   // LIN: pieces issued so far, this step's new pieces start at ring piece lpb and HBM byte
   // lsrc (the stream's byte lsb0 + 1 KiB x pieces issued)
   static_assert(!LIN || (!LM && TBL && !PADC), "LIN: the two-stream row-table pair");
@@ -831,6 +887,22 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
     const int p = ((f + 1) * RB + 1023) / 1024;
     return p < lptot ? p : lptot;
   };
+  // LIN's descriptors of the next step (pipelined as desc_front / desc_row are): nnew pieces
+  // from ring piece lpb (advanced by the previous step's count, one wrap: a step's pieces are
+  // fewer than the ring's -- lin_dma wraps lpb + j the same way) and HBM byte lsrc
+  auto lin_next = [&]() {
+    fcol += PR;
+    frow += PW;
+    const bool wrap = fcol >= W;
+    fcol -= wrap ? W : 0;
+    frow += wrap ? 1 : 0;
+    const int need = lin_need(frontier());
+    lpb += nnew;
+    lpb -= lpb >= lnpr ? lnpr : 0;
+    lsrc += (unsigned)nnew * 1024u;
+    nnew = need - lpdone;
+    lpdone = need;
+  };
   auto lin_dma = [&](int j, int nnew) {
     const bool ok = j < nnew;
     int rp = lpb + j;
@@ -840,11 +912,9 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
         rrs, (__attribute__((address_space(3))) void*)(lds + __builtin_amdgcn_readfirstlane(dst)), 16,
         ok ? lsrc + (unsigned)j * 1024u + (unsigned)lane * 16u : 0xF0000000u, 0, 0, 0);
   };
-  // DMAB: the pair's B waves stream the A-in rows instead of A (A keeps the prologue
-  // rows).  Off: in-kernel stamps (f16x2 res15) give A 3892 cycles per step against
-  // B's 3640 (+ 250 at the barrier), but the four pieces cost B ~420 cycles where they
-  // cost A ~300 -- B then runs 4060 (pair launch 2.03 vs 2.01 ms)
-  constexpr bool DMAB = false;
+  // (The A waves stream the A-in rows.  Moving the step's pieces to the B waves measured
+  // slower -- the four pieces cost B ~420 cycles where they cost A ~300, pair launch 2.03 vs
+  // 2.01 ms -- and that variant is gone.)
 
   // the k-step of the first m-tile that issues DMA piece i, as a map S -> i (-1: none):
   // pieces DSP k-steps apart from k-step 1 (DSP = 1: back to back; 2, 3, 4 measured the
@@ -854,18 +924,15 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
     return (S >= 1 && (S - 1) % DSP == 0 && (S - 1) / DSP < PPW) ? (S - 1) / DSP : -1;
   };
   static_assert(1 + DSP * (PPW - 1) < KSA, "DMA pieces inside the first m-tile");
-  // B's vector-memory operations issued after its step's last DMA piece (its first
-  // m-tile's k-step PPW): that m-tile's later stores, the second m-tile's residual
-  // loads and stores -- the step barrier waits for all but these
-  auto vm_after_dma = []() constexpr {
-    int n = G::NRL + NSTO;
-    for (int i = 0; i < NSTO; ++i) {
-      int ks = (TBL && BAL) ? KET + 2 * G::store_step(i) + 1 : KE + G::store_step(i);
-      if (ks > KSA - 1) ks = KSA - 1;
-      if (ks >= 1 + DSP * (PPW - 1)) ++n;  // (a store on the last piece's k-step issues after it)
-    }
-    return n;
-  };
+  // B's vector-memory operations issued after the pending m-tile's residual loads (its
+  // k-step 0) and before the pending epilogue's first use of them (this m-tile's k-step KE):
+  // the NSTO stores that went out during the pending m-tile (k-steps >= KE) and this m-tile's
+  // residual loads -- every store of this m-tile follows that first use (store_step >= 1).
+  // One wait for all but these ahead of the first use, and the compiler's waitcnt pass finds
+  // every later use of a residual register satisfied: it placed a wait per use (counts it
+  // cannot bound across the loop's back edge, most of them no-ops that still take an issue slot).
+  constexpr int VM_AFTER_RES = NSTO + G::NRL;
+  static_assert(G::store_step(0) >= 1 || NSTO == 0, "no store ahead of the first residual use");
   // One m-tile: KSA k-steps of PRODUCTS x NT MFMAs on the tap bases of `cur`; the
   // operands of step S + PD (or of the next m-tile) load under step S's MFMAs.
   // k-step KW advances the walk, KG derives the next m-tile's geometry; the
@@ -883,16 +950,19 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
       else load_a(rolec, nxt.tq, KStep<SN - KSA>{}, oa[SN % NOA]);
       // the operand reads go out ahead of this step's MFMAs (left to itself the
       // scheduler sinks them below most of the step and then waits on them)
-      __builtin_amdgcn_sched_barrier(0);
+      // (DTOP: A's k-steps 0 and 1 of a step form one scheduling region with the head of the
+      // step's block, where the next step's DMA descriptors land -- see desc_front)
+      constexpr bool DTOP = HONK_PAIR_DTOP && !ISB && FIRST;
+      if constexpr (!(DTOP && S <= 1)) __builtin_amdgcn_sched_barrier(0);
       // the step's other work (walk, geometry, residual loads, DMA, epilogue) issues
       // between its MFMAs (pattern at the end of the step): one wave per SIMD, so VALU
       // work bunched ahead of the MFMAs would leave the matrix pipe idle
       if constexpr (ISB && S == 0) res_loads(rvs[PAR], cur.pix);
       if constexpr (TBL && BAL) {
-        if constexpr (S == KWT) walk_adv_t(wk);
+        if constexpr (S == KWT) walk_adv_t(rolec, wk);
         if constexpr (S >= KGT && S < KGT + 3) geo_row(rolec, wk, nxt, std::integral_constant<int, S - KGT>{});
       } else if constexpr (TBL) {
-        if constexpr (S == KW) walk_adv_t(wk);
+        if constexpr (S == KW) walk_adv_t(rolec, wk);
         if constexpr (S == KG) nxt = geo_t(rolec, wk);
       } else {
         if constexpr (S == KW) walk_adv(wk);
@@ -910,7 +980,7 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
       });
       if constexpr (LIN && !ISB && FIRST && dma_piece(S) >= 0) {
         lin_dma(2 * dma_piece(S) + widx, nnew);
-      } else if constexpr (ISB == DMAB && FIRST && dma_piece(S) >= 0) {
+      } else if constexpr (!ISB && FIRST && dma_piece(S) >= 0) {
         constexpr int i = dma_piece(S);  // this wave's piece p = widx + 2 i: row (p / PPR), part p % PPR
         constexpr int ra = (2 * i) / PPR, rb = (2 * i + 1) / PPR;
         constexpr int pa = (2 * i) % PPR, pb = (2 * i + 1) % PPR;
@@ -918,27 +988,43 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
         dma(widx ? roff[rb] : roff[ra], widx ? rslot[rb] : rslot[ra], std::integral_constant<int, pa>{},
             std::integral_constant<int, pb>{}, rr < nnew);
       }
+      // the next step's DMA descriptors (scalar; see desc_front for where they land)
+      if constexpr (!ISB && !FIRST) {
+        if constexpr (LIN) {
+          if constexpr (S == 1) lin_next();
+        } else {
+          if constexpr (S == 1) desc_front();
+          if constexpr (S >= 2 && S < 2 + MAXR) desc_row(S - 2);
+        }
+      }
       if constexpr (TBL && BAL) {
         if constexpr (S >= KET && S < KET + NHS)
           epi_half(rolec, std::integral_constant<int, S - KET>{}, std::integral_constant<int, 1 - PAR>{});
       } else {
         static_for<ELAST + 1>([&](auto ec) {
           constexpr int E = decltype(ec)::value;
-          if constexpr ((KE + E < KSA ? KE + E : KSA - 1) == S) epi_step(rolec, ec, std::integral_constant<int, 1 - PAR>{});
+          if constexpr ((KE + E < KSA ? KE + E : KSA - 1) == S) {
+            if constexpr (ISB && E == 0) wait_vmcnt<VM_AFTER_RES>();
+            epi_step(rolec, ec, std::integral_constant<int, 1 - PAR>{});
+          }
         });
       }
+      if constexpr (DTOP && S <= 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // the operand read first
       static_for<NPROD * NT>([&](auto) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
         __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // then up to two VALU
-        __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);  // and up to two SALU
+        __builtin_amdgcn_sched_group_barrier(0x004, (DTOP && S <= 1) ? 5 : 2, 0);  // and up to two SALU
       });
-      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (!(DTOP && S == 0)) __builtin_amdgcn_sched_barrier(0);
     });
   };
 
   auto run_role = [&](auto rolec) {
     constexpr bool ISB = decltype(rolec)::value;
-    int fprev = frontier();
+    if constexpr (!ISB) {
+      fprev = frontier();
+      nnew = 0;
+    }
     if constexpr (LIN && !ISB) {
       // prologue: the pieces of rows 0 .. F(-1), the two A waves alternating
       lpdone = lin_need(fprev);
@@ -946,12 +1032,16 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             rrs, (__attribute__((address_space(3))) void*)(lds + __builtin_amdgcn_readfirstlane(ringA + p * 1024)), 16,
             lsb0 + (unsigned)p * 1024u + (unsigned)lane * 16u, 0, 0, 0);
+      // step 0's descriptors
+      lpb = lpdone % lnpr;
+      lsrc = lsb0 + (unsigned)lpdone * 1024u;
+      lin_next();
     } else if constexpr (!ISB) {
       // prologue: rows 0 .. F(-1) (A's band 0, its halo row and band 1's first m-tiles)
       for (int row = 0; row <= fprev; ++row) {
         if ((row & 1) == widx) {
-          const unsigned ro = cur_off(rc);
-          const int so = ringA + rc.slot * a.slotb + padb;
+          const unsigned ro = rc.off;
+          const int so = ringA + rc.slot + padb;
 #pragma unroll
           for (int t = 0; t < PPR; ++t) {
             const unsigned v = (psrc[t >> 1] >> (16 * (t & 1))) & 0xffffu;
@@ -960,10 +1050,12 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
                 v == 0xffffu ? 0xF0000000u : ro + v, 0, 0, 0);
           }
         }
-        cur_adv(rc);
+        cur_adv(rc, 1);
       }
-    } else if constexpr (DMAB) {
-      for (int row = 0; row <= fprev; ++row) cur_adv(rc);
+      // step 0's descriptors
+      desc_front();
+#pragma unroll
+      for (int m = 0; m < MAXR; ++m) desc_row(m);
     }
     const int q0w = (ISB ? -a.lag - P : 0) + 16 * widx;  // the wave's first m-tile
     int qlim = 0;  // TBL: the first stream pixel past the wave's table
@@ -973,19 +1065,22 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
       qlim = (tb + TR) * W;
     }
     auto wk = [&]() {
-      if constexpr (TBL) return walk_init_t(q0w + i16);
+      if constexpr (TBL) return walk_init_t(rolec, q0w + i16);
       else return walk_init(q0w + i16);
     }();
     MG mgs[2];
     if constexpr (TBL) mgs[0] = geo_t(rolec, wk);
     else mgs[0] = geo(wk);
+    // B: the weight loads have landed.  (B's loop never waits for all of its vector-memory
+    // operations, so the compiler cannot tell and kept a vmcnt wait in front of the first use
+    // of every VGPR-resident weight fragment, in every step.  A waits at its first barrier.)
+    if constexpr (ISB) wait_vmcnt<0>();
     for (int k = 0; k < nsteps; ++k) {
       // step barrier: this wave's DMA pieces landed (A), A-out writes visible
       // (the asm memory clobbers keep the compiler from moving LDS accesses across the
       // barrier: __builtin_amdgcn_s_barrier alone is not a memory fence to it)
       asm volatile("" ::: "memory");
       if constexpr (!ISB) wait_vmcnt<0>();
-      else if constexpr (DMAB) wait_vmcnt<vm_after_dma()>();
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
@@ -1000,39 +1095,8 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
       }
       // the first m-tile's first operands (later m-tiles' load under the previous one)
       if (k == 0) static_for<PD>([&](auto stc) { load_a(rolec, mgs[0].tq, stc, oa[decltype(stc)::value]); });
-      int nnew = 0;
-      if constexpr (LIN && !ISB) {
-        fcol += PR;
-        frow += PW;
-        if (fcol >= W) {
-          fcol -= W;
-          ++frow;
-        }
-        const int need = lin_need(frontier());
-        nnew = need - lpdone;
-        lpb = lpdone % lnpr;
-        lsrc = lsb0 + (unsigned)lpdone * 1024u;
-        lpdone = need;
-      } else if constexpr (ISB == DMAB) {
-        // frontier of this step and the rows it loads (scalar)
-        fcol += PR;
-        frow += PW;
-        if (fcol >= W) {
-          fcol -= W;
-          ++frow;
-        }
-        const int fcur = frontier();
-        nnew = fcur - fprev;
-        RowCur t = rc;
-#pragma unroll
-        for (int m = 0; m < MAXR; ++m) {
-          roff[m] = cur_off(t);
-          rslot[m] = t.slot * a.slotb;
-          if (m + 1 < MAXR) cur_adv(t);
-        }
-        for (int m = 0; m < nnew; ++m) cur_adv(rc);
-        fprev = fcur;
-      }
+      // (A: this step's DMA descriptors -- nnew, roff / rslot or LIN's lpb / lsrc -- stand
+      // ready: the previous step's second m-tile, or the prologue, derived them)
       static_for<2>([&](auto itc) {
         constexpr int IT = decltype(itc)::value;
         run_mtile(rolec, std::integral_constant<int, IT>{}, mgs[IT], mgs[1 - IT], wk, nnew);

@@ -11,7 +11,17 @@
 // This file includes res.hip with HONK_RES_VF_TU defined: the device templates and
 // their argument structs only (no host code, no non-template kernels), and defines
 // the two launchers res.hip's forward_bf16 calls.
+//
+// Scheduling choices measured under this unit's flag are set here too.  HONK_PAIR_DTOP (see
+// res_bf16p.inc, run_mtile): the A waves' k-steps 0 and 1 of a step form one scheduling
+// region with the head of the step's block, where the compiler places the next step's DMA
+// descriptor arithmetic, so that it issues under those k-steps' MFMAs instead of ahead of the
+// step's first one -- res15 f16x2 333.7K -> 337.2K clips/s, same box (DESIGN.md §3, round 7;
+// an exp/build_vf_variant.sh build with -DHONK_PAIR_DTOP=0 is the comparison).
 #define HONK_RES_VF_TU 1
+#ifndef HONK_PAIR_DTOP
+#define HONK_PAIR_DTOP 1
+#endif
 #include "res.hip"
 
 namespace honk {
