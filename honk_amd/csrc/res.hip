@@ -43,6 +43,20 @@ namespace honk {
 namespace res {
 constexpr int MW = 4;  // waves along M per workgroup
 
+// A clip count the device holds (honk_res_forward_ordered's re-run rounds): the kernels of a
+// round are launched for n clips and run the first live_clips() of them -- the flagged-clip
+// count *count, limited to cap, past the off clips of the rounds before.  count == nullptr:
+// every clip (the host-planned launches).  One scalar read at kernel entry, workgroup-uniform.
+struct LiveRef {
+  const int* count;
+  int cap, off;
+};
+__device__ __forceinline__ int live_clips(const LiveRef& r, int n) {
+  const int c = __builtin_amdgcn_readfirstlane(*r.count);
+  const int v = (c < r.cap ? c : r.cap) - r.off;
+  return v < 0 ? 0 : (v < n ? v : n);
+}
+
 template <int NT, int MT>
 struct Geo {
   static constexpr int CP = 16 * NT;          // padded channels
@@ -549,14 +563,14 @@ __global__ __launch_bounds__(256) void tail_act_kernel(const __bf16* __restrict_
 // logits[b] = Wout . (sum of the fused per-tile channel sums) / HW + bout
 // bn_scale/bn_shift: the last layer's BatchNorm applied to the channel means
 // (bf16 path, whose activations are pre-BN), or nullptr (fp32 path)
-__global__ __launch_bounds__(256) void tail_sum_kernel(const float* __restrict__ chsum, const float* __restrict__ wout,
-                                                       const float* __restrict__ bout, float* __restrict__ logits,
-                                                       int nparts, int HW, int C, int CP, int NL,
-                                                       const float* __restrict__ bn_scale,
-                                                       const float* __restrict__ bn_shift,
-                                                       const float* __restrict__ cscale,
-                                                       const float* __restrict__ oscale,
-                                                       int* __restrict__ flags, float zmax) {
+__device__ __forceinline__ void tail_sum_body(const float* __restrict__ chsum, const float* __restrict__ wout,
+                                              const float* __restrict__ bout, float* __restrict__ logits,
+                                              int nparts, int HW, int C, int CP, int NL,
+                                              const float* __restrict__ bn_scale,
+                                              const float* __restrict__ bn_shift,
+                                              const float* __restrict__ cscale,
+                                              const float* __restrict__ oscale,
+                                              int* __restrict__ flags, float zmax) {
   // groups of 64 threads sum every ng-th partial (coalesced rows of CP floats), then one
   // thread per channel adds the groups' sums in group order: a fixed order for every clip
   // (the row-band last layer writes 8 waves x MT m-tiles x bands partials per clip; one
@@ -594,6 +608,27 @@ __global__ __launch_bounds__(256) void tail_sum_kernel(const float* __restrict__
     for (int k = 0; k < C; ++k) acc = fmaf(wout[n * C + k], mean[k], acc);
     logits[(int64_t)b * NL + n] = acc + bout[n];
   }
+}
+__global__ __launch_bounds__(256) void tail_sum_kernel(const float* __restrict__ chsum, const float* __restrict__ wout,
+                                                       const float* __restrict__ bout, float* __restrict__ logits,
+                                                       int nparts, int HW, int C, int CP, int NL,
+                                                       const float* __restrict__ bn_scale,
+                                                       const float* __restrict__ bn_shift,
+                                                       const float* __restrict__ cscale,
+                                                       const float* __restrict__ oscale,
+                                                       int* __restrict__ flags, float zmax) {
+  tail_sum_body(chsum, wout, bout, logits, nparts, HW, C, CP, NL, bn_scale, bn_shift, cscale, oscale, flags, zmax);
+}
+// the same for the first live_clips() clips of the launch (a re-run round: no scales, no flags)
+__global__ __launch_bounds__(256) void tail_sum_live_kernel(const float* __restrict__ chsum,
+                                                            const float* __restrict__ wout,
+                                                            const float* __restrict__ bout,
+                                                            float* __restrict__ logits, int nparts, int HW, int C,
+                                                            int CP, int NL, const float* __restrict__ bn_scale,
+                                                            const float* __restrict__ bn_shift, LiveRef live) {
+  if ((int)blockIdx.x >= live_clips(live, (int)gridDim.x)) return;  // whole workgroup, before any barrier
+  tail_sum_body(chsum, wout, bout, logits, nparts, HW, C, CP, NL, bn_scale, bn_shift, nullptr, nullptr, nullptr,
+                0.f);
 }
 
 #endif  // HONK_RES_VF_TU
@@ -668,9 +703,14 @@ template <int NT, int PH, int PW, int FM, bool ONES, int FWB = 0>
 // 4x3-pool instances: res8's conv0m 114 -> 110 us per 4096 clips at 7 workgroups per CU vs 6)
 __global__ __launch_bounds__(256, 7) void conv0m_kernel(const float* __restrict__ x, __bf16* __restrict__ out,
                                                      const float* __restrict__ w0, int Hin, int Win, int H, int W,
-                                                     int C, const float* __restrict__ cscale) {
+                                                     int C, const float* __restrict__ cscale, LiveRef live) {
   constexpr int CP = 16 * NT, P = PH * PW, SP = FM == 1 ? 2 : 1, CB = CP * 2 * SP;
   extern __shared__ __attribute__((aligned(16))) unsigned short c0lds[];  // hi plane, lo plane
+  // live (bf16x3 only, count may be null): the launch's first live_clips() clips -- the others'
+  // workgroups leave here, whole, before any barrier
+  if constexpr (FM == 1) {
+    if (live.count && (int)blockIdx.x >= live_clips(live, (int)gridDim.x)) return;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, i16 = lane & 15;
   const int clip = blockIdx.x;
@@ -1208,8 +1248,15 @@ __global__ __launch_bounds__(1024) void flag_compact_kernel(const int* __restric
   if (t == 1023) *count = part[1023];
 }
 
+// *dst = *src, or 0 for a null src (honk_res_forward_ordered's flagged_count: device to device)
+__global__ void count_out_kernel(const int* __restrict__ src, int* __restrict__ dst) {
+  if (threadIdx.x == 0) *dst = src ? *src : 0;
+}
+
 __global__ __launch_bounds__(256) void gather_clips_kernel(const float* __restrict__ x, const int* __restrict__ list,
-                                                           int hw, float* __restrict__ out) {
+                                                           int hw, float* __restrict__ out, LiveRef live) {
+  // (live: list holds that many entries of this launch's; the slots past them stay stale, unread)
+  if (live.count && (int)blockIdx.x >= live_clips(live, (int)gridDim.x)) return;
   const float* src = x + (size_t)list[blockIdx.x] * hw;
   float* dst = out + (size_t)blockIdx.x * hw;
   for (int i = threadIdx.x; i < hw; i += blockDim.x) dst[i] = src[i];
@@ -1217,8 +1264,9 @@ __global__ __launch_bounds__(256) void gather_clips_kernel(const float* __restri
 
 __global__ __launch_bounds__(64) void scatter_logits_kernel(const float* __restrict__ src,
                                                             const int* __restrict__ list, int n, int NL,
-                                                            float* __restrict__ logits) {
+                                                            float* __restrict__ logits, LiveRef live) {
   const int i = blockIdx.x * 64 + threadIdx.x;
+  if (live.count) n = live_clips(live, n);
   if (i >= n * NL) return;
   logits[(size_t)list[i / NL] * NL + i % NL] = src[i];
 }
@@ -1774,7 +1822,7 @@ static int launch_conv0(const Layout& L, const float* x, OT* out, const float* w
 // else the VALU kernel.  HONK_CONV0=v forces the VALU kernel (A/B experiments).
 template <int NT, int FM, bool ONES>
 static int launch_conv0m_nt(const Layout& L, const float* x, void* out, const float* w0, int64_t n,
-                            hipStream_t st, const float* cscale) {
+                            hipStream_t st, const float* cscale, LiveRef live) {
   const unsigned lds = 2u * (unsigned)((L.Hin + 2) * (L.Win + 2)) * 2u;
   // bf16 with a pool: the shared-layout patch kernel (conv0p_kernel); HONK_CONV0=m keeps conv0m_kernel
   const char* ce = getenv("HONK_CONV0");
@@ -1806,10 +1854,10 @@ static int launch_conv0m_nt(const Layout& L, const float* x, void* out, const fl
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
     if (L.Win == 40)                                                                                    \
       hipLaunchKernelGGL((conv0m_kernel<NT, ph_, pw_, FM, ONES, 42>), dim3((unsigned)n), dim3(256), lds, st, x, \
-                         (__bf16*)out, w0, L.Hin, L.Win, L.H, L.W, L.C, cscale);                        \
+                         (__bf16*)out, w0, L.Hin, L.Win, L.H, L.W, L.C, cscale, live);                  \
     else                                                                                                \
       hipLaunchKernelGGL((conv0m_kernel<NT, ph_, pw_, FM, ONES>), dim3((unsigned)n), dim3(256), lds, st, x, \
-                         (__bf16*)out, w0, L.Hin, L.Win, L.H, L.W, L.C, cscale);                        \
+                         (__bf16*)out, w0, L.Hin, L.Win, L.H, L.W, L.C, cscale, live);                  \
     HONK_LAUNCH_CHECK("res conv0m_kernel");                                                             \
     return HONK_OK;                                                                                     \
   }
@@ -1818,18 +1866,20 @@ static int launch_conv0m_nt(const Layout& L, const float* x, void* out, const fl
   return 1;  // no instance
 }
 template <int FM, bool ONES>
+// live (FM 1 only): the launch's clips that run come from the device (LiveRef)
 static int launch_conv0_16(const Layout& L, const float* x, void* out, const float* w0, int64_t n, hipStream_t st,
-                           const float* cscale = nullptr) {
+                           const float* cscale = nullptr, LiveRef live = LiveRef{nullptr, 0, 0}) {
   const char* e = getenv("HONK_CONV0");
   const bool valu = e && e[0] == 'v';
   const bool fits = 2L * (L.Hin + 3) * (L.Win + 2) * 2 <= 160 * 1024 && n <= 0x7fffffff;
   if (!valu && fits) {
     int rc = 1;
-    if (L.NT == 1) rc = launch_conv0m_nt<1, FM, ONES>(L, x, out, w0, n, st, cscale);
-    else if (L.NT == 2) rc = launch_conv0m_nt<2, FM, ONES>(L, x, out, w0, n, st, cscale);
-    else if (L.NT == 3) rc = launch_conv0m_nt<3, FM, ONES>(L, x, out, w0, n, st, cscale);
+    if (L.NT == 1) rc = launch_conv0m_nt<1, FM, ONES>(L, x, out, w0, n, st, cscale, live);
+    else if (L.NT == 2) rc = launch_conv0m_nt<2, FM, ONES>(L, x, out, w0, n, st, cscale, live);
+    else if (L.NT == 3) rc = launch_conv0m_nt<3, FM, ONES>(L, x, out, w0, n, st, cscale, live);
     if (rc <= 0) return rc;
   }
+  if (live.count) return fail(HONK_ERR_UNSUPPORTED, "the stream-ordered re-run needs the matrix-core conv0 kernel");
   if constexpr (FM == 2) return launch_conv0<_Float16, false, ONES>(L, x, (_Float16*)out, w0, n, st, cscale);
   else return launch_conv0<__bf16, FM == 1, ONES>(L, x, (__bf16*)out, w0, n, st);
 }
@@ -1884,10 +1934,14 @@ bool launch_pairk_vf(int dA, int dB, dim3 gd, dim3 bd, hipStream_t st, const Blo
 
 // flags (f16x2 only, may be null): [batch] the clips' admission flags (clip_scale_kernel,
 // tail_sum_kernel; honk_res_forward re-runs the flagged clips)
+// live (bf16x3 only, count may be null; batch <= chunk): every kernel runs the first
+// live_clips() clips of the batch it is launched for (honk_res_forward_ordered's re-run rounds)
 static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* packed, const float* x,
                         float* logits, int64_t batch, int64_t chunk, void* workspace, hipStream_t st,
-                        int* flags = nullptr) {
+                        int* flags = nullptr, LiveRef live = LiveRef{nullptr, 0, 0}) {
   const int FM = fmt_of(L.prec);  // operand format (res_bf16w.inc)
+  if (live.count && (FM != 1 || batch > chunk || use_n_kernel(L, d, FM)))
+    return fail(HONK_ERR_UNSUPPORTED, "a device-held clip count: bf16x3, one chunk");
   const int SP = sp_of(FM);       // 16-bit elements per channel value
   const size_t act = (size_t)chunk * L.H * L.W * L.CP * SP;
   // this format's packed weight fragments (per layer)
@@ -1936,7 +1990,8 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* pa
                            packed + L.off_range, cscale, (int)n, L.Hin * L.Win, flags ? flags + c0 : nullptr);
         HONK_LAUNCH_CHECK("res clip_scale_kernel");
       }
-      rc = (FM == 1) ? launch_conv0_16<1, true>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st)
+      rc = (FM == 1) ? launch_conv0_16<1, true>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st, nullptr,
+                                                live)
            : (FM == 2) ? launch_conv0_16<2, true>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st, cscale)
                        : launch_conv0_16<0, true>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st);
       if (rc) return rc;
@@ -1971,6 +2026,7 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* pa
             pa.ppr = pp.ppr;
             pa.padb = pp.padb;
             pa.ringpad = pp.ringpad;
+            pa.live = live;
             TimedLaunch tl(st, 2.0 * layer_flop_per_clip * (double)n);
             const dim3 gd(grid), bd(256 * pp.ns * pp.ks);
             if (pp.ks == 2) {
@@ -2009,6 +2065,7 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* pa
             pa.ppr = lp.ppr;
             pa.padb = lp.padb;
             pa.ringpad = lp.ringpad;
+            pa.live = live;
             pa.chsum = chsum;
             TimedLaunch tl(st, layer_flop_per_clip * (double)n);
             const dim3 gd(grid), bd(128 * lp.ns);
@@ -2038,6 +2095,7 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* pa
         while ((1 << a.lgd) < a.dil) ++a.lgd;
         if ((int64_t)n * a.nbc > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
         a.ntiles = (int)(n * a.nbc);
+        a.live = live;
         if (i == L.L) parts_last = a.nbc * 4;
         TimedLaunch tl(st, layer_flop_per_clip * (double)n);
         rc = dispatch_block16w(L.NT, FM, a, st);
@@ -2053,6 +2111,13 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* pa
         HONK_LAUNCH_CHECK("res tail_act_kernel");
         continue;
       }
+      if (live.count) {
+        hipLaunchKernelGGL(tail_sum_live_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
+                           packed + L.off_bout, logits + c0 * L.NL, parts_last, L.H * L.W, L.C, L.CP, L.NL, bn_last,
+                           bn_last + L.CP, live);
+        HONK_LAUNCH_CHECK("res tail_sum_live_kernel (weight-stationary)");
+        continue;
+      }
       hipLaunchKernelGGL(tail_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
                          packed + L.off_bout, logits + c0 * L.NL, parts_last, L.H * L.W, L.C, L.CP, L.NL,
                          bn_last, bn_last + L.CP, tail_cs, packed + L.off_range + HONK_NUM_OUT_SCALE,
@@ -2066,7 +2131,8 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* pa
     int nbc_last = 0;
     for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
       const int64_t n = (batch - c0 < chunk) ? batch - c0 : chunk;
-      rc = (SP == 2) ? launch_conv0_16<1, false>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st)
+      rc = (SP == 2) ? launch_conv0_16<1, false>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st, nullptr,
+                                                 live)
                      : launch_conv0_16<0, false>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st);
       if (rc) return rc;
       for (int i = 1; i <= L.L; ++i) {
@@ -2090,6 +2156,7 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* pa
         a.nb0 = bg.nb0;
         if ((int64_t)n * a.nbc > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
         a.ntiles = (int)(n * a.nbc);
+        a.live = live;
         if (i == L.L) nbc_last = a.nbc;
         TimedLaunch tl(st, layer_flop_per_clip * (double)n);
         rc = dispatch_block16r(pr, SP, a, st);
@@ -2097,6 +2164,13 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* pa
         if (rc) return rc;
       }
       const float* bn_last = packed + L.off_bn + (size_t)2 * L.CP * (L.L - 1);
+      if (live.count) {
+        hipLaunchKernelGGL(tail_sum_live_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
+                           packed + L.off_bout, logits + c0 * L.NL, nbc_last * 8 * pr.MT, L.H * L.W, L.C, L.CP, L.NL,
+                           bn_last, bn_last + L.CP, live);
+        HONK_LAUNCH_CHECK("res tail_sum_live_kernel (bf16 row-band)");
+        continue;
+      }
       hipLaunchKernelGGL(tail_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
                          packed + L.off_bout, logits + c0 * L.NL, nbc_last * 8 * pr.MT, L.H * L.W, L.C, L.CP, L.NL,
                          bn_last, bn_last + L.CP, tail_cs, packed + L.off_range + HONK_NUM_OUT_SCALE, (int*)nullptr, 0.f);
@@ -2403,20 +2477,39 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
   return done(HONK_PREC_F32);
 }
 
-int honk_res_forward(const honk_res_desc* d, const float* packed, const float* x, float* logits,
-                     int64_t batch, void* workspace, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+// honk_res_forward (ordered = false) and honk_res_forward_ordered (true: no host read of
+// the flagged-clip count -- cap and flagged_out are its arguments)
+static int res_forward(const honk_res_desc* d, const float* packed, const float* x, float* logits, int64_t batch,
+                       void* workspace, size_t ws_bytes, void* stream, bool ordered, int64_t cap,
+                       int32_t* flagged_out) {
   Layout L;
   int rc = make_layout(d, &L);
   if (rc) return rc;
   if (batch < 0) return fail(HONK_ERR_ARG, "negative batch");
-  if (batch == 0) return HONK_OK;
+  if (ordered) g_rerun = 0;
+  if (batch == 0) {
+    if (ordered && flagged_out) {
+      hipLaunchKernelGGL(count_out_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const int*)nullptr,
+                         flagged_out);
+      HONK_LAUNCH_CHECK("res count_out_kernel");
+    }
+    return HONK_OK;
+  }
   if (!packed || !x || !logits || !workspace) return fail(HONK_ERR_ARG, "null pointer argument");
   const size_t need = honk_res_workspace_bytes(d, batch);
+  // (the ordered entry enqueues nothing for a shape the kernels do not take: the reason is set)
+  if (ordered && need == 0) return HONK_ERR_UNSUPPORTED;
   if (ws_bytes < need)
     return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   const int64_t chunk = chunk_clips(L, batch);
   g_rerun = 0;
+  if (ordered && flagged_out && !(L.prec == HONK_PREC_F16X2 && f16x2_rerun_on())) {
+    hipLaunchKernelGGL(count_out_kernel, dim3(1), dim3(1), 0, st, (const int*)nullptr, flagged_out);
+    HONK_LAUNCH_CHECK("res count_out_kernel");
+  }
   if (L.prec == HONK_PREC_F16X2 && f16x2_rerun_on()) {
     if (batch > 0x7fffffff) return fail(HONK_ERR_ARG, "f16x2: batch beyond 2^31 clips");
     F16Check p;
@@ -2429,6 +2522,35 @@ int honk_res_forward(const honk_res_desc* d, const float* packed, const float* x
     if (rc) return rc;
     hipLaunchKernelGGL(flag_compact_kernel, dim3(1), dim3(1024), 0, st, flags, batch, list, count);
     HONK_LAUNCH_CHECK("res flag_compact_kernel");
+    if (ordered) {
+      // every round the capacity allows, each on the clips the device's count leaves it: the
+      // round at offset o runs clamp(min(count, cap) - o, 0, n) clips (live_clips), its
+      // other workgroups return at once; flagged clips past cap keep their f16x2 logits
+      if (flagged_out) {
+        hipLaunchKernelGGL(count_out_kernel, dim3(1), dim3(1), 0, st, (const int*)count, flagged_out);
+        HONK_LAUNCH_CHECK("res count_out_kernel");
+      }
+      if (cap <= 0 || cap > batch) cap = batch;
+      const honk_res_desc e = rerun_desc(d);
+      Layout L3;
+      rc = make_layout(&e, &L3);
+      if (rc) return rc;
+      float* gx = (float*)(ws + p.gx);
+      float* glog = (float*)(ws + p.glog);
+      for (int64_t o = 0; o < cap; o += p.rc) {
+        const int64_t n = cap - o < p.rc ? cap - o : p.rc;
+        const LiveRef live{count, (int)cap, (int)o};
+        hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)n), dim3(256), 0, st, x, list + o, L.Hin * L.Win, gx,
+                           live);
+        HONK_LAUNCH_CHECK("res gather_clips_kernel");
+        rc = forward_bf16(L3, &e, packed, gx, glog, n, chunk_clips(L3, n), workspace, st, nullptr, live);
+        if (rc) return rc;
+        hipLaunchKernelGGL(scatter_logits_kernel, dim3((unsigned)cdiv(n * L.NL, 64)), dim3(64), 0, st, glog,
+                           list + o, (int)n, L.NL, logits, live);
+        HONK_LAUNCH_CHECK("res scatter_logits_kernel");
+      }
+      return HONK_OK;
+    }
     int flagged = 0;
     HONK_HIP_CHECK(hipMemcpyAsync(&flagged, count, sizeof(int), hipMemcpyDeviceToHost, st));
     HONK_HIP_CHECK(hipStreamSynchronize(st));
@@ -2442,12 +2564,13 @@ int honk_res_forward(const honk_res_desc* d, const float* packed, const float* x
     float* glog = (float*)(ws + p.glog);
     for (int64_t o = 0; o < flagged; o += p.rc) {
       const int64_t n = flagged - o < p.rc ? flagged - o : p.rc;
-      hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)n), dim3(256), 0, st, x, list + o, L.Hin * L.Win, gx);
+      hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)n), dim3(256), 0, st, x, list + o, L.Hin * L.Win, gx,
+                         LiveRef{nullptr, 0, 0});
       HONK_LAUNCH_CHECK("res gather_clips_kernel");
       rc = forward_bf16(L3, &e, packed, gx, glog, n, chunk_clips(L3, n), workspace, st);
       if (rc) return rc;
       hipLaunchKernelGGL(scatter_logits_kernel, dim3((unsigned)cdiv(n * L.NL, 64)), dim3(64), 0, st, glog, list + o,
-                         (int)n, L.NL, logits);
+                         (int)n, L.NL, logits, LiveRef{nullptr, 0, 0});
       HONK_LAUNCH_CHECK("res scatter_logits_kernel");
     }
     return HONK_OK;
@@ -2502,6 +2625,25 @@ int honk_res_forward(const honk_res_desc* d, const float* packed, const float* x
     }
   }
   return HONK_OK;
+}
+
+extern "C" {
+
+int honk_res_forward(const honk_res_desc* d, const float* packed, const float* x, float* logits,
+                     int64_t batch, void* workspace, size_t ws_bytes, void* stream) {
+  return res_forward(d, packed, x, logits, batch, workspace, ws_bytes, stream, false, 0, nullptr);
+}
+
+int honk_res_forward_ordered(const honk_res_desc* d, const float* packed, const float* x, float* logits,
+                             int64_t batch, void* workspace, size_t ws_bytes, void* stream,
+                             int64_t rerun_capacity, int32_t* flagged_count) {
+  return res_forward(d, packed, x, logits, batch, workspace, ws_bytes, stream, true, rerun_capacity, flagged_count);
+}
+
+int64_t honk_res_rerun_clips(const honk_res_desc* d, int64_t batch) {
+  if (!d || d->precision != HONK_PREC_F16X2 || !f16x2_rerun_on()) return 0;
+  F16Check p;
+  return f16_check_plan(d, batch, &p) ? p.rc : 0;
 }
 
 }  // extern "C"

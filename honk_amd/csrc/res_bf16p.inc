@@ -68,6 +68,7 @@ struct Block16PArgs {
   int ringpad;          // PADC, shared pads: a slot's right pad is the next slot's left pad (ring A's
                         // last slot's: ring B's first), ring B carries one more pad past its last slot
                         // (0: every slot has both pads)
+  LiveRef live;         // bf16x3 (FM 1) only, count may be null: the clips that run, of the launch's nclips
 };
 
 template <int NT, int SP>
@@ -169,8 +170,16 @@ __device__ __forceinline__ void block16p_body(const Block16PArgs& a) {
   // this workgroup's clips, then this stream's share (stream 0 takes the larger half)
   const int GR = gridDim.x;
   const int bid = blockIdx.x;
-  const int w0 = (int)(((long)bid * a.nclips) / GR);
-  const int w1 = (int)(((long)(bid + 1) * a.nclips) / GR);
+  // (a device-held clip count -- FM 1, an ordered re-run round -- takes nclips' place: the live
+  // clips spread over the grid.  A workgroup then walks fewer clips than the host planned for;
+  // plan_pair's lag, ring sizes and pieces per step hold for any shorter stream, and
+  // chunk_bytes stays the allocated range.)
+  int nclips = a.nclips;
+  if constexpr (FM == 1) {
+    if (a.live.count) nclips = live_clips(a.live, a.nclips);
+  }
+  const int w0 = (int)(((long)bid * nclips) / GR);
+  const int w1 = (int)(((long)(bid + 1) * nclips) / GR);
   if (w1 <= w0) return;  // whole workgroup, before any barrier
   const int per = (w1 - w0 + NS - 1) / NS;
   const int s0 = min(w0 + stream * per, w1);

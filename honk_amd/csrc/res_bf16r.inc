@@ -186,6 +186,7 @@ struct Block16RArgs {
   float* chsum;           // last layer: [ntiles][NW][MT][CP] channel sums (one per m-tile), else nullptr
   int H, W, dil, TH, nbc, ntiles;  // nbc = tiles (bands) per clip
   int rem, nb1, nb0;               // band geometry (BandGeo)
+  LiveRef live;  // bf16x3 (SP 2) only, count may be null: the clips that run, of the launch's ntiles / nbc
 };
 
 template <int NT, int MT, int SP, bool LAST, bool RES>
@@ -283,7 +284,12 @@ __global__ __launch_bounds__((G16<NT, MT, SP>::NTHREADS), (G16<NT, MT, SP>::NW /
   const int bid = blockIdx.x;
   const int lb = ((GR & 7) == 0) ? (bid & 7) * (GR >> 3) + (bid >> 3) : bid;
   int tile = lb;
-  if (tile >= a.ntiles) return;  // whole workgroup, before any barrier
+  // (a device-held clip count -- bf16x3, an ordered re-run round: the tiles of its first clips)
+  int ntiles = a.ntiles;
+  if constexpr (SP == 2) {
+    if (a.live.count) ntiles = live_clips(a.live, a.ntiles / a.nbc) * a.nbc;
+  }
+  if (tile >= ntiles) return;  // whole workgroup, before any barrier
 
   const int clip_bytes = H * RB;
   // first row h0 of tile tt (class r, band k): its rows are h0 + j dil
@@ -304,7 +310,7 @@ __global__ __launch_bounds__((G16<NT, MT, SP>::NTHREADS), (G16<NT, MT, SP>::NW /
     int h0;
   };
   auto tile_src = [&](int tt) {
-    const bool valid = tt < a.ntiles;
+    const bool valid = tt < ntiles;
     int b = 0, h0 = 0;
     if (valid) tile_geo(tt, b, h0);
     return Src{clip_rsrc(a.in, b, valid), h0};
@@ -501,9 +507,9 @@ __global__ __launch_bounds__((G16<NT, MT, SP>::NTHREADS), (G16<NT, MT, SP>::NW /
 
   while (true) {
     run_tile(sa0, sa1);
-    if (tile >= a.ntiles) break;
+    if (tile >= ntiles) break;
     run_tile(sa1, sa0);
-    if (tile >= a.ntiles) break;
+    if (tile >= ntiles) break;
   }
   wait_vmcnt<0>();
   {

@@ -170,6 +170,7 @@ struct Block16WArgs {
   float* chsum;       // last layer: [ntiles][NW][CP] channel sums, else nullptr
   int H, W, dil, lgd, TH, ntiles;  // dil = 1 << lgd
   int rem, nb1, nb0, nbc;          // band geometry (BandGeo) for TH
+  LiveRef live;  // bf16x3 (FM 1) only, count may be null: the clips that run, of the launch's ntiles / nbc
 };
 
 template <int NT, int SP, bool LAST, bool RES, int FM = (SP == 2 ? 1 : 0)>
@@ -189,7 +190,12 @@ __global__ __launch_bounds__(256, 1) void block16w_kernel(Block16WArgs a) {
   const int bid = blockIdx.x;
   const int lb = ((GR & 7) == 0) ? (bid & 7) * (GR >> 3) + (bid >> 3) : bid;  // XCD-aware tile order
   int tile = lb;
-  if (tile >= a.ntiles) return;  // whole workgroup, before any barrier
+  // (a device-held clip count -- FM 1, an ordered re-run round: the tiles of its first clips)
+  int ntiles = a.ntiles;
+  if constexpr (FM == 1) {
+    if (a.live.count) ntiles = live_clips(a.live, a.ntiles / a.nbc) * a.nbc;
+  }
+  if (tile >= ntiles) return;  // whole workgroup, before any barrier
 
   // the layer's weight operand, resident for the whole launch
   u32x4 wr[G::WP][KSA][NT];
@@ -306,7 +312,7 @@ __global__ __launch_bounds__(256, 1) void block16w_kernel(Block16WArgs a) {
     int rowoff;  // (h0 - d) * RB: byte offset of image row slot 0
   };
   auto tile_src = [&](int tt) {
-    const bool valid = tt < a.ntiles;
+    const bool valid = tt < ntiles;
     int b = 0, h0 = 0, rows = 0;
     if (valid) tile_geo(tt, b, h0, rows);
     return Src{clip_rsrc(a.in, b, valid), (h0 - d) * RB};
@@ -588,9 +594,9 @@ __global__ __launch_bounds__(256, 1) void block16w_kernel(Block16WArgs a) {
 
   while (true) {
     run_tile(sa0, sa1);
-    if (tile >= a.ntiles) break;
+    if (tile >= ntiles) break;
     run_tile(sa1, sa0);
-    if (tile >= a.ntiles) break;
+    if (tile >= ntiles) break;
   }
   wait_vmcnt<0>();
   static_for<ELAST + 1>([&](auto ec) { epi_step(ec); });

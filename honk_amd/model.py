@@ -149,6 +149,30 @@ def _state_key(tensors, device):
     return (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
 
 
+class CapturedForward:
+    """A captured stream-ordered forward (``SpeechResModel.honk_capture``).
+
+    ``replay(x)`` (also ``__call__``) copies ``x`` into the graph's input buffer, replays
+    the graph on the current stream and returns ``logits``: the graph's STATIC output
+    tensor, which the next replay overwrites (clone it to keep a result).  ``flagged`` is
+    the static 0-dim int32 device tensor holding the last replay's flagged-clip count.
+    Nothing here synchronises."""
+
+    def __init__(self, graph, x, logits, flagged, packed):
+        self.graph, self.x, self.logits, self.flagged = graph, x, logits, flagged
+        self._packed = packed  # the weights the graph reads
+
+    def replay(self, x):
+        if tuple(x.shape) != tuple(self.x.shape) or x.dtype != self.x.dtype or x.device != self.x.device:
+            raise RuntimeError(f"captured for {self.x.dtype} {tuple(self.x.shape)} on {self.x.device}, got "
+                               f"{x.dtype} {tuple(x.shape)} on {x.device}")
+        self.x.copy_(x)
+        self.graph.replay()
+        return self.logits
+
+    __call__ = replay
+
+
 class SpeechResModel(SerializableModule):
     """Deep residual KWS net (res8/15/26[-narrow]); model.py:82-121."""
 
@@ -191,6 +215,15 @@ class SpeechResModel(SerializableModule):
         self.honk_reroute = True
         # training on ROCm tensors: block convs on the gfx950 kernels (False: MIOpen)
         self.honk_native_train = True
+        # True: the eval forward through honk_res_forward_ordered -- no host read of the
+        # f16x2 admission's flagged-clip count, so the call only enqueues work (an
+        # asynchronous forward, capturable: honk_capture).  The count stays on the device
+        # (honk_last_rerun_dev, a 0-dim int32 tensor; honk_last_rerun is then None), and the
+        # bf16x3 re-run takes up to honk_rerun_capacity flagged clips (None: the batch), the
+        # ones past it keeping their f16x2 logits.
+        self.honk_stream_ordered = False
+        self.honk_rerun_capacity = None
+        self.honk_last_rerun_dev = None
 
     # -- reference forward (CPU tensors / training mode): model.py:104-121 --
     # native_convs: training on a ROCm tensor runs the stem (conv0 + relu + pool) on
@@ -392,18 +425,66 @@ class SpeechResModel(SerializableModule):
             self.honk_last_precision = precision or self.honk_precision
             B = x.shape[0]
             out = torch.empty(B, self._honk_desc["n_labels"], dtype=torch.float32, device=x.device)
+            ordered = self.honk_stream_ordered
+            if ordered:
+                self.honk_last_rerun = None
+                self.honk_last_rerun_dev = torch.zeros((), dtype=torch.int32, device=x.device)
             if B == 0:
                 return out
             ws_bytes = lib.honk_res_workspace_bytes(desc, B)
             if ws_bytes == 0:
                 _native.check(-1, "honk_res_workspace_bytes")
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+            if ordered:
+                cap = self.honk_rerun_capacity
+                _native.check(lib.honk_res_forward_ordered(desc, packed.data_ptr(), x.data_ptr(), out.data_ptr(), B,
+                                                           ws.data_ptr(), ws_bytes, _native.stream_handle(x.device),
+                                                           0 if cap is None else int(cap),
+                                                           self.honk_last_rerun_dev.data_ptr()),
+                              "honk_res_forward_ordered")
+                return out
             _native.check(lib.honk_res_forward(desc, packed.data_ptr(), x.data_ptr(), out.data_ptr(), B,
                                                ws.data_ptr(), ws_bytes, _native.stream_handle(x.device)),
                           "honk_res_forward")
             # f16x2: the clips the per-clip admission re-ran in bf16x3 (honk_res_rerun_count)
             self.honk_last_rerun = int(lib.honk_res_rerun_count())
         return out
+
+    def honk_capture(self, x_example):
+        """Capture the stream-ordered eval forward for inputs shaped like ``x_example`` (a
+        float32 ROCm tensor [B, H, W]; eval mode) in a ``torch.cuda.CUDAGraph`` and return
+        a ``CapturedForward``: ``replay(x) -> logits``.
+
+        One eager forward runs first: the once-per-pack synchronisations (weight pack,
+        numerics record, the precision policy's probe, the CU-count query) happen there,
+        outside the capture.  The capture itself is the launches of
+        ``honk_res_forward_ordered`` on the capture stream, with ``honk_rerun_capacity`` as it
+        is now; the flagged-clip count is read by the kernels at every replay, so one graph
+        serves batches with any number of out-of-calibration clips.  A later change of the
+        weights, ``honk_precision`` or ``honk_rerun_capacity`` needs a new capture."""
+        if self.training:
+            raise RuntimeError("honk_capture needs eval mode (module.eval())")
+        if not (torch.is_tensor(x_example) and x_example.is_cuda and x_example.dim() == 3
+                and x_example.dtype == torch.float32 and x_example.shape[0] > 0):
+            raise RuntimeError("honk_capture expects a non-empty float32 [B, H, W] tensor on a ROCm device")
+        prev = self.honk_stream_ordered
+        self.honk_stream_ordered = True
+        try:
+            with torch.no_grad(), torch.cuda.device(x_example.device):
+                static_x = x_example.detach().clone().contiguous()
+                why = self._native_fits(static_x, self._run_precision(static_x))
+                if why is not None:
+                    raise RuntimeError(f"honk_capture: the packed forward does not take this model ({why})")
+                self(static_x)
+                torch.cuda.synchronize(static_x.device)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    static_out = self(static_x)
+                    static_flagged = self.honk_last_rerun_dev
+                packed = self._packed(static_x)
+        finally:
+            self.honk_stream_ordered = prev
+        return CapturedForward(graph, static_x, static_out, static_flagged, packed)
 
     def _native_fits(self, x, precision):
         """None if the packed forward (honk_res_forward) takes this model and input shape,

@@ -49,10 +49,18 @@ class LabelService(object):
 
 
 class TorchLabelService(LabelService):
-    """service.py:72-104 (hard-wired cnn-trad-pool2, like the reference)."""
+    """service.py:72-104 (hard-wired cnn-trad-pool2, like the reference).
+
+    ``honk_graph`` (opt-in, default False): with a ``SpeechResModel`` as ``self.model`` on a
+    ROCm device, ``label()`` replays a captured batch-1 stream-ordered forward
+    (``SpeechResModel.honk_capture``, captured at the first call) instead of launching the
+    forward's kernels one by one; ``reload()`` drops the capture."""
+
+    honk_graph = False
 
     def __init__(self, model_filename, no_cuda=False, labels=["_silence_", "_unknown_", "command", "random"],
-                 audio_processor=None):
+                 audio_processor=None, honk_graph=False):
+        self.honk_graph = honk_graph
         self.labels = labels
         self.model_filename = model_filename
         self.no_cuda = no_cuda
@@ -60,6 +68,7 @@ class TorchLabelService(LabelService):
         self.reload()
 
     def reload(self):
+        self._honk_captured = None
         config = model.find_config(model.ConfigType.CNN_TRAD_POOL2)
         config["n_labels"] = len(self.labels)  # mutates the shared dict, as service.py:82 does
         self.model = model.SpeechModel(config)
@@ -77,11 +86,21 @@ class TorchLabelService(LabelService):
             return torch.from_numpy(np.stack([self.audio_processor.compute_mfccs(p).squeeze(2) for p in pcm]))
         return self.audio_processor.compute_mfccs_batch(torch.from_numpy(pcm).cuda())
 
+    def _forward1(self, model_in):
+        """The model's forward of label()'s batch-1 input: the captured one where honk_graph asks for it."""
+        m = self.model
+        if not (self.honk_graph and isinstance(m, model.SpeechResModel) and model_in.is_cuda and not m.training):
+            return m(model_in)
+        cap = getattr(self, "_honk_captured", None)
+        if cap is None or cap[0] is not m or tuple(cap[1].x.shape) != tuple(model_in.shape):
+            cap = self._honk_captured = (m, m.honk_capture(model_in))
+        return cap[1].replay(model_in)
+
     def label(self, wav_data):
         """Labels audio data as one of the trained labels -> (most likely label, probability)."""
         model_in = self._model_input([wav_data])
         with torch.no_grad():
-            predictions = F.softmax(self.model(model_in).squeeze(0).cpu(), dim=0).numpy()
+            predictions = F.softmax(self._forward1(model_in).squeeze(0).cpu(), dim=0).numpy()
         return (self.labels[np.argmax(predictions)], np.max(predictions))
 
     def label_batch(self, windows):

@@ -15,7 +15,10 @@
  * Conventions: every pointer named x/logits/packed/tensors[i]/workspace is a
  * DEVICE pointer (hipMalloc / torch caching allocator); `stream` is a
  * hipStream_t passed as void*.  Work is enqueued on `stream`; no call
- * synchronises or allocates device memory.  Global state: a thread-local
+ * allocates device memory, and none synchronises except honk_res_forward in
+ * HONK_PREC_F16X2 with its admission on (one hipStreamSynchronize per call, to
+ * read the flagged-clip count; honk_res_forward_ordered is the same forward
+ * without it) and honk_res_numerics (once per pack).  Global state: a thread-local
  * last-error string, a per-device CU-count cache, and the mutex-guarded
  * timing window of honk_timing_enable/read (off unless enabled; a diagnostic,
  * not used by the forward itself).  Status: 0 = ok, <0 = error, see
@@ -165,14 +168,46 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
  * averaged away there), or whose f16x2 logits are not finite while its input is, is
  * re-run in BF16X3 and its logits replaced.  This is the one honk_res_forward mode that
  * SYNCHRONISES `stream` (once per call, to read the flagged-clip count; not capturable
- * in a hipGraph).  HONK_F16X2_RERUN=0 in the environment turns the admission off (raw
- * f16x2: kernel tests).  The workspace (honk_res_workspace_bytes) includes its buffers.
+ * in a hipGraph -- honk_res_forward_ordered below is).  HONK_F16X2_RERUN=0 in the
+ * environment turns the admission off (raw f16x2: kernel tests).  The workspace
+ * (honk_res_workspace_bytes) includes its buffers.
  */
 int honk_res_forward(const honk_res_desc* d, const float* packed, const float* x, float* logits,
                      int64_t batch, void* workspace, size_t workspace_bytes, void* stream);
 #define HONK_F16X2_Z_MAX 8
-/* The clips the calling thread's last honk_res_forward re-ran in bf16x3 (0 unless F16X2). */
+/* The clips the calling thread's last honk_res_forward re-ran in bf16x3 (0 unless F16X2;
+   0 after honk_res_forward_ordered: the host does not learn the count). */
 int64_t honk_res_rerun_count(void);
+/*
+ * The same forward, STREAM-ORDERED in every mode: it only enqueues kernels on `stream` --
+ * no copy to the host, no stream / device / event synchronisation, no allocation, no
+ * stream or event creation -- so it returns before the work has run and can be captured
+ * in a hipGraph.  (An open honk_timing_enable window records events around the block
+ * launches, as in honk_res_forward; leave it closed while capturing.)  Same workspace
+ * (honk_res_workspace_bytes), same status codes.
+ *
+ * F32 / BF16 / BF16X3, and F16X2 with HONK_F16X2_RERUN=0: the launches and the logits of
+ * honk_res_forward.  F16X2 with the admission: the f16x2 pass, the flags and the compacted
+ * list of flagged clips as in honk_res_forward; then, since the host does not know how
+ * many clips were flagged, ceil(cap / rc) re-run rounds are enqueued unconditionally
+ * (cap = rerun_capacity, or batch when rerun_capacity <= 0 or > batch; rc =
+ * honk_res_rerun_clips).  Every kernel of the round at offset o reads the flagged count
+ * from device memory and works on its first clamp(min(count, cap) - o, 0, rc) clips; the
+ * workgroups of the others return at once (a round nothing is left for costs its empty
+ * launches).  Flagged clips past the first cap, in batch order, KEEP THEIR F16X2 LOGITS.
+ *
+ * flagged_count (device int32, may be NULL): receives the batch's flagged-clip count, not
+ * limited to cap (written by a kernel on `stream`; 0 in the modes without an admission):
+ * *flagged_count > cap, read later, tells the caller that the re-run overflowed.
+ * batch == 0: HONK_OK; 0 is written to flagged_count when it is not NULL (`stream` must
+ * then be valid), nothing else is enqueued.
+ */
+int honk_res_forward_ordered(const honk_res_desc* d, const float* packed, const float* x, float* logits,
+                             int64_t batch, void* workspace, size_t workspace_bytes, void* stream,
+                             int64_t rerun_capacity, int32_t* flagged_count /* device, may be NULL */);
+/* Host-only: the clips one bf16x3 re-run round of the f16x2 admission takes for `batch`
+   clips (both entry points), or 0: not F16X2, the admission off, or an unsupported shape. */
+int64_t honk_res_rerun_clips(const honk_res_desc* d, int64_t batch);
 
 /* ---- SpeechModel (cnn-*); utils/model.py:123-205 ------------------------------ */
 typedef struct honk_cnn_desc {
