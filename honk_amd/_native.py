@@ -39,6 +39,13 @@ class CnnDesc(ctypes.Structure):
         "has_lin", "dnn1", "dnn2", "dnn1_relu", "precision")]
 
 
+class MfccWindowsPlan(ctypes.Structure):
+    """honk_mfcc_windows_plan_t."""
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "windows", "shared_frames", "edge_frames", "frames_computed", "workspace_bytes")] + [
+        ("shared", ctypes.c_int32), ("frames", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "honk_res_packed_floats": (ctypes.c_size_t, [ctypes.POINTER(ResDesc)]),
@@ -133,6 +140,12 @@ _PROTOS = {
                                 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "honk_mfcc_f32": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                      c_f32p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p, ctypes.c_void_p]),
+    "honk_mfcc_windows_plan": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_int64] * 2
+                               + [ctypes.c_void_p]),
+    "honk_mfcc_windows_i16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                             c_f32p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p, ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.c_void_p]),
     "honk_spatial_mean_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_spatial_mean_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_cross_entropy_f32": (ctypes.c_int, [c_f32p, ctypes.c_void_p, c_f32p, ctypes.c_int64, ctypes.c_int32,

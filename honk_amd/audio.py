@@ -117,3 +117,71 @@ class AudioPreprocessor(object):
                                                 dct.shape[0], out[s0:].data_ptr(), _native.stream_handle(pcm.device)),
                               "honk_mfcc_f32")
         return out
+
+    # -- strided windows of one recording (libhonk_hip.so honk_mfcc_windows_i16) ---------
+    def windows_plan(self, samples, stride, window=16000, first=0, count=0):
+        """honk_mfcc_windows_plan for this front end's n_fft / hop -> (status, MfccWindowsPlan); host-only."""
+        import ctypes
+        from . import _native
+        plan = _native.MfccWindowsPlan()
+        rc = _native.load().honk_mfcc_windows_plan(int(samples), int(window), int(stride), self.n_fft,
+                                                   self.hop_length, int(first), int(count), ctypes.addressof(plan))
+        return rc, plan
+
+    def compute_mfccs_windows(self, pcm, stride, window=16000, first=0, count=None):
+        """pcm: 1-D int16 torch tensor, one recording -> [count, frames, n_dct] float32: the MFCC of the
+        windows ``pcm[w*stride : w*stride + window] / 32768`` for w in [first, first + count) (count None:
+        up to the recording's last whole window), as ``service.stride`` yields them.
+
+        ROCm device: honk_mfcc_windows_i16 (csrc/mfcc_stream.hip; each STFT frame once where
+        stride % hop == 0), nothing sliced on the host.  CPU: ``compute_mfccs`` per window."""
+        import torch
+        from . import _native
+        if pcm.dim() != 1 or pcm.dtype != torch.int16:
+            raise ValueError("compute_mfccs_windows: pcm must be a 1-D int16 tensor")
+        stride, window, first = int(stride), int(window), int(first)
+        if stride < 1 or window < 1 or first < 0:
+            raise ValueError("compute_mfccs_windows: stride >= 1, window >= 1, first >= 0")
+        S = pcm.shape[0]
+        W = 0 if S < window else 1 + (S - window) // stride
+        count = max(0, W - first) if count is None else int(count)
+        if count < 0 or first + count > W:
+            raise ValueError(f"compute_mfccs_windows: windows [{first}, {first + count}) of {W}")
+        frames, n_dct = 1 + window // self.hop_length, self.dct_filters.shape[0]
+        if not pcm.is_cuda:
+            x = pcm.numpy()
+            if count == 0:
+                return torch.empty(0, frames, n_dct, dtype=torch.float32)
+            return torch.from_numpy(np.stack([
+                self.compute_mfccs(x[w * stride:w * stride + window].astype(np.float32) / 32768.).squeeze(2)
+                for w in range(first, first + count)]))
+        pcm = pcm.contiguous()
+        out = torch.empty(count, frames, n_dct, dtype=torch.float32, device=pcm.device)
+        if count == 0:
+            return out
+        rc, plan = self.windows_plan(S, stride, window, first, count)
+        if rc == -2:  # HONK_ERR_UNSUPPORTED: a shape outside the kernel's plan -> the per-window kernel
+            x = (pcm.float() * (1.0 / 32768.0)).unfold(0, window, stride)[first:first + count]
+            return self.compute_mfccs_batch(x.contiguous())
+        _native.check(rc, "honk_mfcc_windows_plan")
+        win, mel, dct = self._device_tables(pcm.device)
+        ws = self._windows_workspace(pcm.device, plan.workspace_bytes)
+        with torch.cuda.device(pcm.device):
+            rc = _native.load().honk_mfcc_windows_i16(
+                pcm.data_ptr(), S, window, stride, first, count, win.data_ptr(), self.n_fft, self.hop_length,
+                mel.data_ptr(), mel.shape[0], dct.data_ptr(), n_dct, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                _native.stream_handle(pcm.device))
+        if rc == -2:
+            x = (pcm.float() * (1.0 / 32768.0)).unfold(0, window, stride)[first:first + count]
+            return self.compute_mfccs_batch(x.contiguous())
+        _native.check(rc, "honk_mfcc_windows_i16")
+        return out
+
+    def _windows_workspace(self, device, nbytes):
+        import torch
+        key = str(device)
+        cache = getattr(self, "_dev_ws", {})
+        if key not in cache or cache[key].numel() < nbytes:
+            cache[key] = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+            self._dev_ws = cache
+        return cache[key]

@@ -1,0 +1,390 @@
+// Strided-window MFCC of one long recording (the /listen front end): every window of
+// `window` samples at stride `stride` of an int16 recording in device memory ->
+// out [n_windows][frames][n_dct], the model input -- each STFT frame computed once.
+//
+// compute_mfccs reflect-pads every window on its own, so only the frames whose n_fft
+// span crosses a window edge are window-specific (frames 0, 1, 99, 100 of the 101 at
+// n_fft 480 / hop 160).  With stride % hop == 0 an interior frame f of window w is the
+// global frame w * (stride / hop) + f of the recording, whichever window asks for it.
+//
+// One kernel, one workgroup per tile of FT frame slots.  A tile is made of groups: a
+// group is a run of consecutive frames of one (real or virtual) window, staged in LDS
+// as one contiguous reflected span of the recording (int16 -> fp32 * 2^-15, exact):
+//   segment tiles  one group of FT frames: consecutive shared interior frames of the
+//                  whole range (the "virtual window" from the first selected window's
+//                  start to the last one's end, where no interior frame reflects), or,
+//                  where windows leave gaps / on the unshared route, of one window;
+//   edge tiles     FT / gs groups of gs slots: the head frames [0, flo) or the tail
+//                  frames (fhi, frames) of one window, about that window's own bounds.
+// The power spectrum is mfcc_mfma_kernel's GEMM (v_mfma_f32_16x16x4_f32, twiddle x
+// window fragments built from LDS tables); a frame is one column of it, so its result
+// depends on its own n_fft samples only, in a fixed order.  Power goes to an LDS tile;
+// mel, log and DCT are fixed-order loops over that tile (no floating-point atomics);
+// the finished frames are scattered from LDS to every (window, frame) that maps to them.
+#include "common.h"
+
+namespace honk {
+namespace mfccs {
+
+constexpr int WAVES = 4;
+constexpr int MT = 2;        // frame tiles of 16 per workgroup
+constexpr int FT = 16 * MT;  // frame slots per workgroup
+constexpr int PADK = 8;      // floats inserted after every hop samples of a staged span: the slot stride is
+                             // hop + 8 = 168 floats = 42 16-B slots.  A ds_read_b128 lane group is 8 frames at
+                             // k-offset 4g and 8 at 4(g+1): 42 i mod 16 puts the first on the even slots of the
+                             // 256-B bank row and the second on the odd ones (no conflict; hop alone is 4-way)
+constexpr int MAX_MELS = 128;  // the mel-range table of the (fixed-size) workspace
+
+enum { MODE_UNSHARED = 0, MODE_OVERLAP = 1, MODE_GAPPED = 2 };
+
+struct Args {
+  const int16_t* pcm;
+  const float* window;  // [n_fft]
+  const float* melw;    // [n_mels][n_bins]
+  const float* dct;     // [n_dct][n_mels]
+  const int* mrange;    // [n_mels][2] first, last nonzero bin of a mel row (workspace)
+  float* out;           // [n][frames][n_dct]
+  int64_t first_sample;  // first_window * stride
+  int64_t n;             // windows of the range
+  int64_t G;             // MODE_OVERLAP: shared frames of the range
+  int64_t seg_tiles;     // segment tiles; the edge tiles follow
+  int stride, win_len, n_fft, hop, n_bins, n_mels, n_dct, frames;
+  int flo, fhi;  // interior frames [flo, fhi] (flo > fhi: none)
+  int mode, q;   // q = stride / hop (shared modes)
+  int tps;       // per-window modes: segment tiles per window
+  int gs, gpt, gspan;  // edge tiles: slots per group, groups per tile, LDS floats per group
+  int xs_floats;
+};
+
+struct Group {
+  int64_t base;  // sample of the (virtual) window's start
+  int64_t L;     // its length: reflection bound
+  int64_t wl;    // window (relative to the range) of slot 0; MODE_OVERLAP: unused
+  int64_t f0;    // frame of slot 0
+  int nf;        // frames (0: an empty group)
+};
+
+__device__ __forceinline__ int64_t reflect(int64_t i, int64_t n) {
+  // numpy 'reflect' padding (no edge repeat), valid for |overhang| < n
+  if (i < 0) return -i;
+  if (i >= n) return 2 * n - 2 - i;
+  return i;
+}
+
+__device__ __forceinline__ Group group_of(const Args& a, int64_t t, int gi) {
+  Group g;
+  if (t < a.seg_tiles) {
+    if (a.mode == MODE_OVERLAP) {
+      g.base = a.first_sample;
+      g.L = (a.n - 1) * a.stride + a.win_len;
+      g.wl = 0;
+      g.f0 = a.flo + t * FT;
+      g.nf = (int)min((int64_t)FT, a.G - t * FT);
+    } else {
+      const int fa = a.mode == MODE_GAPPED ? a.flo : 0;
+      const int fb = a.mode == MODE_GAPPED ? a.fhi + 1 : a.frames;
+      g.wl = t / a.tps;
+      g.base = a.first_sample + g.wl * a.stride;
+      g.L = a.win_len;
+      g.f0 = fa + (int)(t % a.tps) * FT;
+      g.nf = min(FT, fb - (int)g.f0);
+    }
+  } else {
+    const int64_t gid = (t - a.seg_tiles) * a.gpt + gi;
+    g.wl = gid >> 1;
+    g.base = a.first_sample + g.wl * a.stride;
+    g.L = a.win_len;
+    const bool tail = gid & 1;
+    g.f0 = tail ? a.fhi + 1 : 0;
+    g.nf = (g.wl < a.n && gi < a.gpt) ? (tail ? a.frames - 1 - a.fhi : a.flo) : 0;
+  }
+  return g;
+}
+
+// first / last bin with a nonzero weight of every mel row (last < first: an all-zero row);
+// one wave per row
+__global__ __launch_bounds__(64) void mel_range_kernel(const float* melw, int n_bins, int* mrange) {
+  const int m = blockIdx.x;
+  int lo = n_bins, hi = -1;
+  for (int k = threadIdx.x; k < n_bins; k += 64)
+    if (melw[(int64_t)m * n_bins + k] != 0.f) {
+      lo = min(lo, k);
+      hi = max(hi, k);
+    }
+  for (int o = 32; o; o >>= 1) {
+    lo = min(lo, __shfl_xor(lo, o));
+    hi = max(hi, __shfl_xor(hi, o));
+  }
+  if (threadIdx.x == 0) {
+    mrange[2 * m] = hi < 0 ? 0 : lo;
+    mrange[2 * m + 1] = hi;
+  }
+}
+
+__global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int N = a.n_fft, NB = a.n_bins, NM = a.n_mels, ND = a.n_dct, hop = a.hop, pad = N / 2;
+  const int PS = NB | 1;            // odd row stride of the power tile
+  float* xs = sm;                   // [xs_floats] staged spans; log-mel and output tiles later
+  float* win = xs + a.xs_floats;    // [N]
+  float* tw = win + N;              // [2N] cos | -sin
+  float* pw = tw + 2 * N;           // [FT][PS] power
+  float* lm = xs;                   // [FT][NM + 1] log-mel (after the GEMM)
+  float* ot = lm + FT * (NM + 1);   // [FT][ND + 1] finished frames
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, i16 = lane & 15;
+  const int64_t t = blockIdx.x;
+  const bool edge = t >= a.seg_tiles;
+  const int gs = edge ? a.gs : FT, ng = edge ? a.gpt : 1, gspan = edge ? a.gspan : 0;
+  const int glen = (gs - 1) * hop + N;
+
+  for (int gi = 0; gi < ng; ++gi) {
+    const Group gr = group_of(a, t, gi);
+    const int have = gr.nf > 0 ? (gr.nf - 1) * hop + N : 0;
+    const int64_t off0 = gr.f0 * hop - pad;
+    float* xg = xs + gi * gspan;
+    for (int i = tid; i < glen; i += blockDim.x) {
+      float v = 0.f;
+      if (i < have) v = (float)a.pcm[gr.base + reflect(off0 + i, gr.L)] * (1.f / 32768.f);
+      xg[i + PADK * (i / hop)] = v;
+    }
+  }
+  for (int k = tid; k < N; k += blockDim.x) {
+    float sn, cs;
+    sincosf(6.283185307179586f * (float)k / (float)N, &sn, &cs);
+    win[k] = a.window[k];
+    tw[k] = cs;
+    tw[N + k] = -sn;
+  }
+  __syncthreads();
+
+  // this lane's frame slots: 16 m + i16 -> LDS offset of the slot's first sample
+  int soff[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int s = 16 * m + i16;
+    const int gi = s / gs, fi = s - gi * gs;
+    soff[m] = gi < ng ? gi * gspan + fi * (hop + PADK) : 0;
+  }
+  const int ntiles = (2 * NB + 15) / 16;
+  const int nkb = N / 16;
+  for (int ct = wave; ct < ntiles; ct += WAVES) {
+    // this lane's T row: column c = 16 ct + i16 -> bin c/2, cos (even) / -sin (odd)
+    const int c = 16 * ct + i16;
+    const int bin = c >> 1;
+    const float* twp = tw + ((c & 1) ? N : 0);
+    const int bstep = (int)(((int64_t)bin * 16) % N);
+    const int bj = bin % N;
+    int idx = (int)(((int64_t)bin * (4 * g)) % N);  // (bin * k) mod N at k = 16 kb + 4 g
+    f32x4 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kb = 0; kb < nkb; ++kb) {
+      const int k0 = 16 * kb + 4 * g;
+      const int koff = k0 + PADK * ((16 * kb) / hop);  // hop % 16 == 0: a k-block stays in one hop
+      float tv[4];
+      int ij = idx;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        tv[j] = twp[ij] * win[k0 + j];
+        ij += bj;
+        if (ij >= N) ij -= N;
+      }
+      idx += bstep;
+      if (idx >= N) idx -= N;
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        const f32x4 sv = *(const f32x4*)(xs + soff[m] + koff);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv[j], sv[j], acc[m], 0, 0, 0);
+      }
+    }
+    // lane holds D[c = 16 ct + 4 g + r][slot 16 m + i16]: bins 8 ct + 2 g + {0, 1}
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+#pragma unroll
+      for (int qq = 0; qq < 2; ++qq) {
+        const int bb = 8 * ct + 2 * g + qq;
+        if (bb < NB)
+          pw[(16 * m + i16) * PS + bb] = acc[m][2 * qq] * acc[m][2 * qq] + acc[m][2 * qq + 1] * acc[m][2 * qq + 1];
+      }
+    }
+  }
+  __syncthreads();
+  // mel filterbank over each row's nonzero bins, ascending; log of the positive entries
+  for (int e = tid; e < FT * NM; e += blockDim.x) {
+    const int f = e % FT, m = e / FT;
+    const float* w = a.melw + (int64_t)m * NB;
+    const int lo = a.mrange[2 * m], hi = a.mrange[2 * m + 1];
+    float s = 0.f;
+    for (int k = lo; k <= hi; ++k) s = fmaf(w[k], pw[f * PS + k], s);
+    lm[f * (NM + 1) + m] = s > 0.f ? logf(s) : s;
+  }
+  __syncthreads();
+  for (int e = tid; e < FT * ND; e += blockDim.x) {
+    const int f = e % FT, i = e / FT;
+    const float* d = a.dct + (int64_t)i * NM;
+    float s = 0.f;
+    for (int m = 0; m < NM; ++m) s = fmaf(d[m], lm[f * (NM + 1) + m], s);
+    ot[f * (ND + 1) + i] = s;
+  }
+  // where each slot goes: output rows row0 + d (frames - q), d < count -- window wl0 + d, frame f0 - d q
+  int64_t* srow = (int64_t*)(ot + FT * (ND + 1));  // [FT] (8-byte aligned: FT is even)
+  int* scnt = (int*)(srow + FT);                   // [FT]
+  const bool fan = !edge && a.mode == MODE_OVERLAP;
+  if (tid < FT) {
+    const int gi = tid / gs, fi = tid - gi * gs;
+    int64_t row = 0;
+    int cnt = 0;
+    if (gi < ng) {
+      const Group gr = group_of(a, t, gi);
+      if (fi < gr.nf) {
+        if (fan) {
+          const int64_t jl = gr.f0 + fi;  // frame of the virtual window: frame jl - w q of window w
+          const int64_t wlo = jl > a.fhi ? (jl - a.fhi + a.q - 1) / a.q : 0;
+          const int64_t whi = min(a.n - 1, (jl - a.flo) / a.q);
+          row = wlo * a.frames + (jl - wlo * a.q);
+          cnt = (int)(whi - wlo + 1);
+        } else {
+          row = gr.wl * a.frames + gr.f0 + fi;
+          cnt = 1;
+        }
+      }
+    }
+    srow[tid] = row;
+    scnt[tid] = cnt;
+  }
+  __syncthreads();
+  const int cmax = fan ? (a.fhi - a.flo) / a.q + 1 : 1;
+  const int per = cmax * ND;
+  const int64_t rstep = fan ? a.frames - a.q : 0;
+  for (int e = tid; e < FT * per; e += blockDim.x) {
+    const int s = e / per, r = e - s * per;
+    const int d = r / ND, i = r - d * ND;
+    if (d < scnt[s]) a.out[(srow[s] + d * rstep) * ND + i] = ot[s * (ND + 1) + i];
+  }
+}
+
+struct Plan {
+  honk_mfcc_windows_plan_t p;
+  int flo, fhi, mode, q, gs;
+};
+
+// host-only; status and reason as the entry points return them
+static int make_plan(int64_t samples, int32_t window, int32_t stride, int32_t n_fft, int32_t hop,
+                     int64_t first_window, int64_t n_windows, Plan* pl) {
+  if (samples < 0 || first_window < 0 || n_windows < 0) return fail(HONK_ERR_ARG, "negative count");
+  if (stride < 1 || n_fft < 2 || hop < 1) return fail(HONK_ERR_ARG, "bad mfcc window arguments");
+  if (window <= n_fft / 2) return fail(HONK_ERR_ARG, "reflect padding needs window > n_fft/2");
+  const int64_t W = samples < window ? 0 : 1 + (samples - window) / stride;
+  if (first_window > W || n_windows > W - first_window)
+    return fail(HONK_ERR_ARG, "window range past the recording's %lld windows", (long long)W);
+  if (n_fft % 16 || hop % 16) return fail(HONK_ERR_UNSUPPORTED, "mfcc windows: n_fft and hop must be multiples of 16");
+  const int pad = n_fft / 2, frames = 1 + window / hop;
+  pl->flo = (pad + hop - 1) / hop;
+  pl->fhi = window >= pad ? (window - pad) / hop : -1;
+  if (pl->fhi > frames - 1) pl->fhi = frames - 1;
+  const int nint = pl->fhi - pl->flo + 1;
+  const bool shared = stride % hop == 0 && nint > 0;
+  pl->q = shared ? stride / hop : 0;
+  pl->mode = !shared ? MODE_UNSHARED : (pl->q <= nint ? MODE_OVERLAP : MODE_GAPPED);
+  const int nh = pl->flo, nt = frames - 1 - pl->fhi;
+  pl->gs = nh > nt ? nh : nt;
+  if (shared && pl->gs > FT) return fail(HONK_ERR_UNSUPPORTED, "mfcc windows: %d edge frames per side", pl->gs);
+  honk_mfcc_windows_plan_t& p = pl->p;
+  p.windows = W;
+  p.frames = frames;
+  p.shared = shared ? 1 : 0;
+  if (!shared) {
+    p.shared_frames = p.edge_frames = 0;
+    p.frames_computed = n_windows * frames;
+  } else {
+    p.shared_frames = n_windows == 0 ? 0 : (pl->mode == MODE_OVERLAP ? (n_windows - 1) * pl->q + nint : n_windows * nint);
+    p.edge_frames = n_windows * (frames - nint);
+    p.frames_computed = p.shared_frames + p.edge_frames;
+  }
+  p.workspace_bytes = 2 * MAX_MELS * (int64_t)sizeof(int);
+  return HONK_OK;
+}
+
+}  // namespace mfccs
+}  // namespace honk
+
+using namespace honk;
+
+extern "C" int honk_mfcc_windows_plan(int64_t samples, int32_t window, int32_t stride, int32_t n_fft, int32_t hop,
+                                      int64_t first_window, int64_t n_windows, honk_mfcc_windows_plan_t* plan) {
+  if (!plan) return fail(HONK_ERR_ARG, "null pointer argument");
+  mfccs::Plan pl;
+  const int rc = mfccs::make_plan(samples, window, stride, n_fft, hop, first_window, n_windows, &pl);
+  if (rc != HONK_OK) return rc;
+  *plan = pl.p;
+  return HONK_OK;
+}
+
+extern "C" int honk_mfcc_windows_i16(const int16_t* pcm_i16, int64_t samples, int32_t window, int32_t stride,
+                                     int64_t first_window, int64_t n_windows, const float* window_tbl, int32_t n_fft,
+                                     int32_t hop, const float* mel_weights, int32_t n_mels, const float* dct,
+                                     int32_t n_dct, float* out, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  using namespace mfccs;
+  if (n_mels < 1 || n_dct < 1) return fail(HONK_ERR_ARG, "bad mfcc arguments");
+  Plan pl;
+  const int rc = make_plan(samples, window, stride, n_fft, hop, first_window, n_windows, &pl);
+  if (rc != HONK_OK) return rc;
+  if (n_windows == 0) return HONK_OK;
+  if (!pcm_i16 || !window_tbl || !mel_weights || !dct || !out || !workspace)
+    return fail(HONK_ERR_ARG, "null pointer argument");
+  if (n_mels > MAX_MELS) return fail(HONK_ERR_UNSUPPORTED, "mfcc windows: more than %d mel bands", MAX_MELS);
+  if (workspace_bytes < (size_t)pl.p.workspace_bytes)
+    return fail(HONK_ERR_WORKSPACE, "mfcc windows workspace: %zu bytes, %lld needed", workspace_bytes,
+                (long long)pl.p.workspace_bytes);
+  Args a;
+  a.pcm = pcm_i16; a.window = window_tbl; a.melw = mel_weights; a.dct = dct; a.mrange = (const int*)workspace;
+  a.out = out;
+  a.first_sample = first_window * stride;
+  a.n = n_windows;
+  a.stride = stride; a.win_len = window; a.n_fft = n_fft; a.hop = hop; a.n_bins = n_fft / 2 + 1;
+  a.n_mels = n_mels; a.n_dct = n_dct; a.frames = pl.p.frames;
+  a.flo = pl.flo; a.fhi = pl.fhi; a.mode = pl.mode; a.q = pl.q;
+  a.G = pl.p.shared_frames;
+  a.tps = 1; a.gs = 1; a.gpt = 0; a.gspan = 0;
+  int64_t edge_tiles = 0;
+  const int seg_floats = (FT - 1) * hop + n_fft + PADK * (FT + n_fft / hop);
+  int xs = seg_floats;
+  if (pl.mode == MODE_OVERLAP) {
+    a.seg_tiles = cdiv(a.G, FT);
+  } else {
+    const int nfw = pl.mode == MODE_GAPPED ? pl.fhi - pl.flo + 1 : a.frames;
+    a.tps = (int)cdiv(nfw, FT);
+    a.seg_tiles = n_windows * a.tps;
+  }
+  if (pl.mode != MODE_UNSHARED && pl.gs > 0) {
+    a.gs = pl.gs;
+    a.gpt = FT / pl.gs;
+    // floats of a group's padded span, rounded up to 16 mod 32: with gs = 2 the 8 groups of a lane
+    // group's slots then fall on distinct slot pairs of the bank row, as the segment tiles' slots do
+    int gspan = (pl.gs - 1) * hop + n_fft + PADK * (pl.gs + n_fft / hop);
+    gspan = (gspan + 15) / 32 * 32 + 16;
+    a.gspan = gspan;
+    edge_tiles = cdiv(2 * n_windows, a.gpt);
+    if (a.gpt * gspan > xs) xs = a.gpt * gspan;
+  }
+  // the log-mel and output tiles and the slots' destination table reuse the span area
+  const int tail_floats = FT * (n_mels + 1) + FT * (n_dct + 1) + 3 * FT;
+  if (tail_floats > xs) xs = tail_floats;
+  a.xs_floats = (xs + 3) / 4 * 4;
+  const int64_t tiles = a.seg_tiles + edge_tiles;
+  const size_t lds = sizeof(float) * ((size_t)a.xs_floats + 3 * (size_t)n_fft + (size_t)FT * (a.n_bins | 1));
+  if (lds > 160 * 1024) return fail(HONK_ERR_UNSUPPORTED, "mfcc windows: n_fft / hop too large for the LDS plan");
+  if (tiles > 0x7fffffff) return fail(HONK_ERR_UNSUPPORTED, "mfcc windows: too many frame tiles in one call");
+  hipLaunchKernelGGL(mel_range_kernel, dim3((unsigned)n_mels), dim3(64), 0, (hipStream_t)stream, mel_weights, a.n_bins,
+                     (int*)workspace);
+  HONK_LAUNCH_CHECK("mel_range_kernel");
+  if (lds > 64 * 1024)  // (the plan's ceiling, so every shape and a captured call find it set)
+    HONK_HIP_CHECK(hipFuncSetAttribute((const void*)mfcc_windows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024));
+  hipLaunchKernelGGL(mfcc_windows_kernel, dim3((unsigned)tiles), dim3(64 * WAVES), lds, (hipStream_t)stream, a);
+  HONK_LAUNCH_CHECK("mfcc_windows_kernel");
+  return HONK_OK;
+}

@@ -124,6 +124,76 @@ class TorchLabelService(LabelService):
         return dict(contains_command=False) if method == "command_tagging" else labels
 
 
+    def label_stream(self, wav_data, stride_size_ms=500, max_windows=8192):
+        """[(label, prob)] of every 1 s window at ``stride_size_ms`` of a recording, in order:
+        ``label_batch(list(stride(...)))`` with the front end on the device.  The int16 bytes are
+        uploaded once; the windows go through ``compute_mfccs_windows`` (each STFT frame computed
+        once), the model's forward and the softmax ``max_windows`` at a time, so memory stays
+        bounded whatever the recording's length."""
+        stride_bytes = int(2 * 16000 * stride_size_ms / 1000)
+        if stride_bytes < 1:
+            raise ValueError("label_stream: stride_size_ms too small")
+        if self.no_cuda or stride_bytes % 2:
+            return self.label_batch(list(stride(wav_data, stride_bytes, 2 * 16000)))
+        if max_windows < 1:
+            raise ValueError("label_stream: max_windows >= 1")
+        n = len(wav_data) // 2
+        total = 0 if n < 16000 else 1 + (n - 16000) // (stride_bytes // 2)
+        if total == 0:
+            return []
+        device = next(self.model.parameters()).device
+        pcm = torch.from_numpy(np.frombuffer(wav_data, dtype=np.int16, count=n).copy()).to(device)
+        out = []
+        with torch.no_grad():
+            for w0 in range(0, total, max_windows):
+                x = self.audio_processor.compute_mfccs_windows(pcm, stride_bytes // 2, 16000, w0,
+                                                               min(max_windows, total - w0))
+                p = F.softmax(self.model(x).cpu(), dim=1).numpy()
+                out.extend((self.labels[int(np.argmax(r))], float(np.max(r))) for r in p)
+        return out
+
+    def listen_stream(self, wav_data, stride_size_ms=500, method="labels", keyword="command", min_keyword_prob=0.85):
+        """``listen`` over ``label_stream``: the same return contract and early-exit order."""
+        labels = {}
+        for label, prob in self.label_stream(wav_data, stride_size_ms):
+            labels[label] = labels.get(label, 0.0) + float(prob)
+            if label == keyword and prob >= min_keyword_prob and method == "command_tagging":
+                return dict(contains_command=True)
+        return dict(contains_command=False) if method == "command_tagging" else labels
+
+
+class StreamListener(object):
+    """Incremental ``label_stream``: ``feed(wav_bytes)`` returns the (label, prob) of the windows the
+    bytes fed so far complete, in order; any chunking of a recording into ``feed`` calls yields the
+    windows of ``label_stream`` on the whole recording.  Between calls it keeps only the unconsumed
+    tail (less than one window plus one stride)."""
+
+    def __init__(self, service, stride_size_ms=500):
+        self.service = service
+        self.stride_size_ms = stride_size_ms
+        self._stride = int(2 * 16000 * stride_size_ms / 1000)
+        self._window = 2 * 16000
+        self._buf = b""
+        self._skip = 0  # bytes before the next window's start still to come (stride > window)
+
+    def feed(self, wav_bytes):
+        wav_bytes = bytes(wav_bytes)
+        if self._skip:
+            drop = min(self._skip, len(wav_bytes))
+            self._skip -= drop
+            wav_bytes = wav_bytes[drop:]
+        self._buf += wav_bytes
+        if len(self._buf) < self._window:
+            return []
+        done = 1 + (len(self._buf) - self._window) // self._stride
+        out = self.service.label_stream(self._buf, self.stride_size_ms)
+        assert len(out) == done
+        nxt = done * self._stride
+        self._skip = max(0, nxt - len(self._buf))
+        self._buf = self._buf[nxt:]
+        return out
+
+
 def stride(array, stride_size, window_size):
     """service.py:106-110: sliding windows (server.py:104 uses 0.5 s stride, 1 s window)."""
     i = 0

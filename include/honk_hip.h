@@ -299,6 +299,44 @@ int honk_conv_same_wgrad_f32(const float* x, const float* dy, float* dw, int64_t
 int honk_mfcc_f32(const float* pcm, int64_t batch, int32_t samples, const float* window, int32_t n_fft,
                   int32_t hop, const float* mel_weights, int32_t n_mels, const float* dct, int32_t n_dct,
                   float* out, void* stream);
+/*
+ * The same front end over a long recording (the /listen serving path, server.py:99-112):
+ * every window of `window` samples that starts at sample w * stride of the int16 recording
+ * pcm_i16 [samples] (device; converted x * 2^-15 in fp32, exact).  The recording has
+ *   W = samples < window ? 0 : 1 + (samples - window) / stride
+ * windows; the call computes windows [first_window, first_window + n_windows) into
+ * out [n_windows][1 + window/hop][n_dct] fp32, each as honk_mfcc_f32 would from its own
+ * samples (reflect padding about the window's own bounds).  With stride % hop == 0 the
+ * frames whose n_fft span lies inside a window are frames of the recording: each is
+ * computed once and written to every window that contains it; only the frames that cross a
+ * window edge (0, 1, 99, 100 of the 101 at n_fft 480 / hop 160) are per window.  Otherwise
+ * every frame is computed per window (no sharing, still no host slicing).  A frame's
+ * n_dct values are a function of its n_fft samples alone (fixed summation order, no
+ * floating-point atomics): ranges, chunks and shifted recordings agree bit for bit.
+ *
+ * honk_mfcc_windows_plan (host-only, no GPU work) fills the counts for a range and the
+ * workspace size.  honk_mfcc_windows_i16 only enqueues on `stream` (no synchronisation,
+ * no allocation: capturable).  HONK_ERR_ARG: a null pointer, a negative count, stride < 1,
+ * window <= n_fft/2, a range past W; HONK_ERR_WORKSPACE: a short workspace;
+ * HONK_ERR_UNSUPPORTED (reason in honk_last_error): n_fft or hop not a multiple of 16,
+ * more than 128 mel bands, a shape past the kernel's LDS plan -- run honk_mfcc_f32 on the
+ * windows then.  n_windows == 0: HONK_OK, nothing enqueued.
+ */
+typedef struct honk_mfcc_windows_plan_t {
+  int64_t windows;         /* W of the whole recording                                   */
+  int64_t shared_frames;   /* frames of the range computed once for all their windows    */
+  int64_t edge_frames;     /* frames of the range computed per window (shared route)     */
+  int64_t frames_computed; /* their sum; n_windows * frames on the unshared route        */
+  int64_t workspace_bytes;
+  int32_t shared;          /* 1: the shared route (stride % hop == 0), 0: per window     */
+  int32_t frames;          /* 1 + window / hop                                           */
+} honk_mfcc_windows_plan_t;
+int honk_mfcc_windows_plan(int64_t samples, int32_t window, int32_t stride, int32_t n_fft, int32_t hop,
+                           int64_t first_window, int64_t n_windows, honk_mfcc_windows_plan_t* plan);
+int honk_mfcc_windows_i16(const int16_t* pcm_i16, int64_t samples, int32_t window, int32_t stride,
+                          int64_t first_window, int64_t n_windows, const float* window_tbl, int32_t n_fft,
+                          int32_t hop, const float* mel_weights, int32_t n_mels, const float* dct, int32_t n_dct,
+                          float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training (data-parallel train(), utils/train.py:99-135) -------------------- */
 /*
