@@ -46,6 +46,11 @@ class MfccWindowsPlan(ctypes.Structure):
         ("shared", ctypes.c_int32), ("frames", ctypes.c_int32)]
 
 
+class PcenParams(ctypes.Structure):
+    """honk_pcen_params_t (defaults: HONK_PCEN_* of include/honk_hip.h)."""
+    _fields_ = [(n, ctypes.c_float) for n in ("eps", "s", "alpha", "delta", "r")] + [("power", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "honk_res_packed_floats": (ctypes.c_size_t, [ctypes.POINTER(ResDesc)]),
@@ -146,6 +151,8 @@ _PROTOS = {
                                              ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                              c_f32p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p, ctypes.c_void_p,
                                              ctypes.c_size_t, ctypes.c_void_p]),
+    "honk_pcen_f32": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                     c_f32p, ctypes.c_int32, ctypes.c_void_p, c_f32p, ctypes.c_void_p]),
     "honk_spatial_mean_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_spatial_mean_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_cross_entropy_f32": (ctypes.c_int, [c_f32p, ctypes.c_void_p, c_f32p, ctypes.c_int64, ctypes.c_int32,

@@ -10,8 +10,21 @@ periodic Hann window, power spectrum, Slaney mel filterbank with area
 normalisation, ``log`` of the positive entries, a 40x40 DCT-II basis from
 ``librosa.filters.dct``).  Output layout matches the reference: (frames, 40, 1)
 float32, which ``collate_fn`` (model.py:258) reshapes to [1, 101, 40].
+
+PCEN front end (``compute_pcen``, manage_audio.py:28,44-47; ``collate_fn``'s other branch,
+model.py:253-265): PARITY UNPINNED as well -- the reference's ``pcen`` package
+(``StreamingPCENTransform``) is not available, so this restates the published algorithm
+(Wang et al. 2017) on the STFT and mel filterbank above:
+``E = mel @ |X|^power``; ``M[0] = E[0]``, ``M[t] = (1 - s) M[t-1] + s E[t]`` per band, reset
+for every clip; ``out = (E / (M + eps)^alpha + delta)^r - delta^r``, [frames, n_mels], no DCT.
+The defaults (``PCEN_DEFAULTS``) follow that package as best they can be restated without it;
+pinning its exact choices later changes defaults, not code.  CPU path: numpy
+(``compute_pcen``); ROCm path: ``compute_pcen_batch`` -> ``honk_pcen_f32`` (csrc/pcen.hip).
+Checked against the independent float64 restatement tests/pcen_ref.py.
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 
@@ -55,9 +68,15 @@ def dct_filters(n_filters, n_input):
     return basis
 
 
+# PCEN parameters (HONK_PCEN_* of include/honk_hip.h); the smoother starts at M[0] = E[0]
+PCEN_DEFAULTS = dict(eps=1e-6, s=0.025, alpha=0.98, delta=2.0, r=0.5, power=1)
+
+
 class AudioPreprocessor(object):
-    def __init__(self, sr=16000, n_dct_filters=40, n_mels=40, f_max=4000, f_min=20, n_fft=480, hop_ms=10):
+    def __init__(self, sr=16000, n_dct_filters=40, n_mels=40, f_max=4000, f_min=20, n_fft=480, hop_ms=10,
+                 pcen_params=None):
         self.n_mels = n_mels
+        self.pcen_params = dict(PCEN_DEFAULTS, **(pcen_params or {}))
         self.dct_filters = dct_filters(n_dct_filters, n_mels)
         self.sr = sr
         self.f_max = f_max if f_max is not None else sr // 2
@@ -68,15 +87,17 @@ class AudioPreprocessor(object):
         n = np.arange(n_fft)
         self._window = (0.5 - 0.5 * np.cos(2.0 * np.pi * n / n_fft)).astype(np.float32)
 
-    def melspectrogram(self, y):
+    def _stft(self, y):
         y = np.asarray(y, dtype=np.float32)
         pad = self.n_fft // 2
         y = np.pad(y, (pad, pad), mode="reflect")
         n_frames = 1 + (len(y) - self.n_fft) // self.hop_length
         idx = np.arange(self.n_fft)[None, :] + self.hop_length * np.arange(n_frames)[:, None]
         frames = y[idx] * self._window[None, :]
-        spec = np.fft.rfft(frames, n=self.n_fft, axis=1).astype(np.complex64)
-        power = (np.abs(spec) ** 2).astype(np.float32).T  # (bins, frames)
+        return np.fft.rfft(frames, n=self.n_fft, axis=1).astype(np.complex64)  # (frames, bins)
+
+    def melspectrogram(self, y):
+        power = (np.abs(self._stft(y)) ** 2).astype(np.float32).T  # (bins, frames)
         return self._mel @ power  # (n_mels, frames)
 
     def compute_mfccs(self, data):
@@ -85,6 +106,64 @@ class AudioPreprocessor(object):
         data[pos] = np.log(data[pos])
         out = (self.dct_filters @ data).T  # (frames, n_dct)
         return np.asfortranarray(out[:, :, None]).astype(np.float32)
+
+    # -- PCEN (module docstring; PARITY UNPINNED) ------------------------------------
+    def _pcen_clip(self, y):
+        """y: [S] -> [frames, n_mels] float32."""
+        p = self.pcen_params
+        if p["power"] not in (1, 2):
+            raise ValueError("pcen: power must be 1 or 2")
+        mag = np.abs(self._stft(y)).astype(np.float32)
+        E = ((mag * mag if p["power"] == 2 else mag) @ self._mel.T).astype(np.float32)  # (frames, n_mels)
+        s, a = np.float32(p["s"]), np.float32(1.0) - np.float32(p["s"])
+        M = np.empty_like(E)
+        M[0] = E[0]
+        for t in range(1, E.shape[0]):
+            M[t] = a * M[t - 1] + s * E[t]
+        r, delta = np.float32(p["r"]), np.float32(p["delta"])
+        gain = np.power(M + np.float32(p["eps"]), -np.float32(p["alpha"]))
+        return (np.power(E * gain + delta, r) - np.power(np.zeros_like(E) + delta, r)).astype(np.float32)
+
+    def compute_pcen(self, data):
+        """data: numpy or CPU torch, [S], [1, S] or [B, S] -> torch float32 [B, frames, n_mels] (the
+        reference hands in [1, S] and concatenates along dim 0); the smoother restarts for every clip."""
+        import torch
+        if isinstance(data, torch.Tensor):
+            data = data.detach().cpu().numpy()
+        data = np.asarray(data, dtype=np.float32)
+        if data.ndim == 1:
+            data = data[None]
+        if data.ndim != 2:
+            raise ValueError("compute_pcen: data must be [S], [1, S] or [B, S]")
+        frames = 1 + data.shape[1] // self.hop_length
+        out = np.empty((data.shape[0], frames, self.n_mels), np.float32)
+        for i, y in enumerate(data):
+            out[i] = self._pcen_clip(y)
+        return torch.from_numpy(out)
+
+    def compute_pcen_batch(self, pcm):
+        """pcm: torch float32 [B, samples] -> [B, frames, n_mels] on pcm's device: honk_pcen_f32 on a ROCm
+        device (chunks of 65535 clips), ``compute_pcen`` on the CPU."""
+        import torch
+        from . import _native
+        if not pcm.is_cuda:
+            return self.compute_pcen(pcm)
+        pcm = pcm.contiguous().float()
+        B, S = pcm.shape
+        win, mel, _ = self._device_tables(pcm.device)
+        frames = 1 + S // self.hop_length
+        out = torch.empty(B, frames, mel.shape[0], dtype=torch.float32, device=pcm.device)
+        p = self.pcen_params
+        params = _native.PcenParams(p["eps"], p["s"], p["alpha"], p["delta"], p["r"], int(p["power"]))
+        lib = _native.load()
+        with torch.cuda.device(pcm.device):
+            for s0 in range(0, B, 65535):
+                n = min(65535, B - s0)
+                _native.check(lib.honk_pcen_f32(pcm[s0:].data_ptr(), n, S, win.data_ptr(), self.n_fft,
+                                                self.hop_length, mel.data_ptr(), mel.shape[0], ctypes.addressof(params),
+                                                out[s0:].data_ptr(), _native.stream_handle(pcm.device)),
+                              "honk_pcen_f32")
+        return out
 
     # -- batched GPU path (libhonk_hip.so honk_mfcc_f32) ---------------------------
     def _device_tables(self, device):

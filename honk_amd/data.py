@@ -12,15 +12,17 @@ without a host round trip per clip.
   over this dataset draws exactly the batches (and sampler RNG) the reference's does.
 * ``device_batch(indices)`` = ``augment_batch`` (DeviceAugment.load_batch: the
   reference's ``random`` draws per clip in batch order, its audio cache, one
-  ``honk_augment_f32`` launch) followed by ``honk_mfcc_f32``
-  (AudioPreprocessor.compute_mfccs_batch): the model input [B, 101, 40].
+  ``honk_augment_f32`` launch) followed by the front end ``audio_preprocess_type``
+  names, as ``collate_fn`` branches (model.py:253-265): "MFCCs" -> ``honk_mfcc_f32``
+  (AudioPreprocessor.compute_mfccs_batch), "PCEN" -> ``honk_pcen_f32``
+  (compute_pcen_batch; the smoother restarts for every clip).  Either way the model
+  input [B, 101, 40].
 
 ``train()`` / ``evaluate()`` (honk_amd/train.py) call ``device_batch`` on the
 loader's indices whenever the dataset has it.  The augmentation is bit-exact to the
-reference's ``load_audio`` (tests/golden/augment.npz); the MFCC stage is parity
-UNPINNED (librosa absent; checked against oracle/mfcc_ref.py).  Only the MFCC
-front end exists on the device (``audio_preprocess_type`` "MFCCs"; PCEN is out of
-scope).  ROCm tensors only: there is no CPU fallback in the product path.
+reference's ``load_audio`` (tests/golden/augment.npz); both front ends are parity
+UNPINNED (librosa and the ``pcen`` package absent; checked against oracle/mfcc_ref.py
+and tests/pcen_ref.py).  ROCm tensors only: there is no CPU fallback in the product path.
 """
 from __future__ import annotations
 
@@ -54,8 +56,10 @@ class DeviceSpeechDataset(data.Dataset):
         n_dct_filters, audio_preprocess_type); rng: the ``random`` stream the draws
         come from (the module itself by default, as in the reference)."""
         super().__init__()
-        if config.get("audio_preprocess_type", "MFCCs") != "MFCCs":
-            raise ValueError("DeviceSpeechDataset: only the MFCC front end runs on the device")
+        self.audio_preprocess_type = config.get("audio_preprocess_type", "MFCCs")
+        if self.audio_preprocess_type not in ("MFCCs", "PCEN"):
+            raise ValueError(f"DeviceSpeechDataset: audio_preprocess_type {self.audio_preprocess_type!r} "
+                             "(the front ends are \"MFCCs\" and \"PCEN\")")
         self.audio_files = list(clips.keys())
         self.audio_labels = [int(v[1]) for v in clips.values()]
         self.set_type = set_type
@@ -100,8 +104,11 @@ class DeviceSpeechDataset(data.Dataset):
 
     def device_batch(self, indices):
         """The model input [B, frames, n_dct] of a batch of dataset indices (augmentation,
-        then the MFCCs of collate_fn, model.py:253-265)."""
-        return self.audio_processor.compute_mfccs_batch(self.augment_batch(indices))
+        then the MFCCs or the PCEN of collate_fn, model.py:253-265)."""
+        pcm = self.augment_batch(indices)
+        if self.audio_preprocess_type == "PCEN":
+            return self.audio_processor.compute_pcen_batch(pcm)
+        return self.audio_processor.compute_mfccs_batch(pcm)
 
 
 def batch_input(dataset, model_in):

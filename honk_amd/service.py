@@ -54,12 +54,19 @@ class TorchLabelService(LabelService):
     ``honk_graph`` (opt-in, default False): with a ``SpeechResModel`` as ``self.model`` on a
     ROCm device, ``label()`` replays a captured batch-1 stream-ordered forward
     (``SpeechResModel.honk_capture``, captured at the first call) instead of launching the
-    forward's kernels one by one; ``reload()`` drops the capture."""
+    forward's kernels one by one; ``reload()`` drops the capture.
+
+    ``audio_preprocess_type`` ("MFCCs", the default, or "PCEN"): the front end the checkpoint was
+    trained with (the reference's ``--audio_preprocess_type``).  PCEN restarts its smoother for every
+    window, as the reference's ``compute_pcen`` resets its transform after every clip."""
 
     honk_graph = False
 
     def __init__(self, model_filename, no_cuda=False, labels=["_silence_", "_unknown_", "command", "random"],
-                 audio_processor=None, honk_graph=False):
+                 audio_processor=None, honk_graph=False, audio_preprocess_type="MFCCs"):
+        if audio_preprocess_type not in ("MFCCs", "PCEN"):
+            raise ValueError(f"TorchLabelService: audio_preprocess_type {audio_preprocess_type!r}")
+        self.audio_preprocess_type = audio_preprocess_type
         self.honk_graph = honk_graph
         self.labels = labels
         self.model_filename = model_filename
@@ -78,10 +85,14 @@ class TorchLabelService(LabelService):
         self.model.eval()
 
     def _model_input(self, windows):
-        """int16 PCM byte windows -> [B, frames, 40] MFCC on the model's device.
+        """int16 PCM byte windows -> [B, frames, 40] MFCC (or PCEN) on the model's device.
 
-        ROCm: one batched honk_mfcc_f32 launch (csrc/mfcc.hip); CPU: numpy."""
+        ROCm: one batched honk_mfcc_f32 / honk_pcen_f32 call (csrc/mfcc.hip, csrc/pcen.hip); CPU: numpy."""
         pcm = np.stack([np.frombuffer(w, dtype=np.int16) for w in windows]).astype(np.float32) / 32768.
+        if self.audio_preprocess_type == "PCEN":
+            if self.no_cuda:
+                return self.audio_processor.compute_pcen(pcm)
+            return self.audio_processor.compute_pcen_batch(torch.from_numpy(pcm).cuda())
         if self.no_cuda:
             return torch.from_numpy(np.stack([self.audio_processor.compute_mfccs(p).squeeze(2) for p in pcm]))
         return self.audio_processor.compute_mfccs_batch(torch.from_numpy(pcm).cuda())
@@ -129,7 +140,8 @@ class TorchLabelService(LabelService):
         ``label_batch(list(stride(...)))`` with the front end on the device.  The int16 bytes are
         uploaded once; the windows go through ``compute_mfccs_windows`` (each STFT frame computed
         once), the model's forward and the softmax ``max_windows`` at a time, so memory stays
-        bounded whatever the recording's length."""
+        bounded whatever the recording's length.  Under PCEN the windows are device-side slices of
+        the uploaded recording through ``compute_pcen_batch`` (every window its own smoother)."""
         stride_bytes = int(2 * 16000 * stride_size_ms / 1000)
         if stride_bytes < 1:
             raise ValueError("label_stream: stride_size_ms too small")
@@ -143,11 +155,16 @@ class TorchLabelService(LabelService):
             return []
         device = next(self.model.parameters()).device
         pcm = torch.from_numpy(np.frombuffer(wav_data, dtype=np.int16, count=n).copy()).to(device)
-        out = []
+        out, pcmf = [], None
         with torch.no_grad():
             for w0 in range(0, total, max_windows):
-                x = self.audio_processor.compute_mfccs_windows(pcm, stride_bytes // 2, 16000, w0,
-                                                               min(max_windows, total - w0))
+                nw = min(max_windows, total - w0)
+                if self.audio_preprocess_type == "PCEN":
+                    if pcmf is None:
+                        pcmf = (pcm.float() * (1.0 / 32768.0)).unfold(0, 16000, stride_bytes // 2)
+                    x = self.audio_processor.compute_pcen_batch(pcmf[w0:w0 + nw].contiguous())
+                else:
+                    x = self.audio_processor.compute_mfccs_windows(pcm, stride_bytes // 2, 16000, w0, nw)
                 p = F.softmax(self.model(x).cpu(), dim=1).numpy()
                 out.extend((self.labels[int(np.argmax(r))], float(np.max(r))) for r in p)
         return out

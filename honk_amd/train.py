@@ -10,8 +10,8 @@ Differences, both additive: ``evaluate``/``train`` accept injected loaders /
 datasets (the reference builds them from ``SpeechDataset.splits``, which needs
 the Speech Commands folders and librosa -- out of scope); a
 ``honk_amd.data.DeviceSpeechDataset`` is consumed on the device (its batches are
-clip indices: ``load_audio``'s augmentation and ``collate_fn``'s MFCCs run as
-kernels, honk_amd/data.py).
+clip indices: ``load_audio``'s augmentation and ``collate_fn``'s front end -- MFCCs or,
+with ``--audio_preprocess_type PCEN``, PCEN -- run as kernels, honk_amd/data.py).
 """
 from __future__ import annotations
 
@@ -109,7 +109,7 @@ def evaluate(config, model=None, test_loader=None):
     weighted, total = [], 0
     with torch.no_grad():
         for model_in, labels in test_loader:
-            model_in = batch_input(test_loader.dataset, model_in)  # device datasets: indices -> MFCCs
+            model_in = batch_input(test_loader.dataset, model_in)  # device datasets: indices -> MFCCs / PCEN
             if not config["no_cuda"]:
                 model_in, labels = model_in.cuda(), labels.cuda()
             scores = model(model_in)
@@ -213,7 +213,7 @@ def _train_epochs(config, model, train_set, dev_set, train_loader, dev_loader, s
             optimizer.zero_grad()
             reducer.reset()
             labels_host = labels
-            # a DeviceSpeechDataset batch is clip indices: augmentation + MFCC on the device
+            # a DeviceSpeechDataset batch is clip indices: augmentation + MFCC / PCEN on the device
             model_in = batch_input(train_set, model_in)
             if not config["no_cuda"]:
                 model_in, labels = model_in.cuda(), labels.cuda()

@@ -338,6 +338,39 @@ int honk_mfcc_windows_i16(const int16_t* pcm_i16, int64_t samples, int32_t windo
                           int32_t hop, const float* mel_weights, int32_t n_mels, const float* dct, int32_t n_dct,
                           float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PCEN front-end (AudioPreprocessor.compute_pcen, utils/manage_audio.py:28,44-47) ---- */
+/*
+ * Per-channel energy normalisation (Wang et al. 2017), PARITY UNPINNED: the reference's
+ * `pcen` package is not available, so this is the published algorithm and the defaults
+ * below restate that package as best they can be without it.  For each clip of
+ * pcm [batch][samples] f32, with honk_mfcc_f32's STFT (centre reflect padding, the
+ * caller's window [n_fft] and mel_weights [n_mels][n_fft/2+1], device, f32):
+ *   E[t][m] = sum_k mel_weights[m][k] * |X_t[k]|^power      power 1 (magnitude) or 2
+ *   M[0] = E[0];  M[t] = (1 - s) M[t-1] + s E[t]            per band, reset for every clip
+ *   out[t][m] = (E / (M + eps)^alpha + delta)^r - delta^r
+ * out [batch][1 + samples/hop][n_mels] f32; no DCT.  The smoother starts at M[0] = E[0]
+ * (HONK_PCEN_INIT_FIRST_FRAME, the only initial state built); zero energy gives exactly 0.
+ * params == NULL: the HONK_PCEN_* defaults.  Only enqueues on `stream` (no synchronisation,
+ * no allocation, no workspace: capturable); batch <= 65535 per call; batch == 0: HONK_OK.
+ * One launch when frames <= 112, n_fft % 16 == 0, hop % 4 == 0 and the LDS plan fits (the
+ * MFMA MFCC kernel's shapes), else two (mel energies into out, then a segmented scan in
+ * place); HONK_MFCC_VALU=1 in the environment forces the latter.  HONK_ERR_ARG: a null
+ * pointer, samples <= n_fft/2, s outside (0, 1], eps <= 0, alpha < 0, delta < 0, r <= 0,
+ * power not 1 or 2, a non-finite parameter; HONK_ERR_UNSUPPORTED: n_fft past the two-launch
+ * route's LDS plan as well.
+ */
+#define HONK_PCEN_EPS 1e-6f
+#define HONK_PCEN_S 0.025f
+#define HONK_PCEN_ALPHA 0.98f
+#define HONK_PCEN_DELTA 2.0f
+#define HONK_PCEN_R 0.5f
+#define HONK_PCEN_POWER 1
+#define HONK_PCEN_INIT_FIRST_FRAME 1 /* M[0] = E[0] */
+typedef struct { float eps, s, alpha, delta, r; int32_t power; } honk_pcen_params_t;
+int honk_pcen_f32(const float* pcm, int64_t batch, int32_t samples, const float* window, int32_t n_fft,
+                  int32_t hop, const float* mel_weights, int32_t n_mels,
+                  const honk_pcen_params_t* params /* NULL = defaults */, float* out, void* stream);
+
 /* ---- training (data-parallel train(), utils/train.py:99-135) -------------------- */
 /*
  * One torch.optim.SGD step (dampening 0) over a flat fp32 parameter bucket whose
