@@ -1645,6 +1645,11 @@ static PairPlan pair_at(const Layout& L, const honk_res_desc* d, int FM, int64_t
   const int sB = dB == dA ? 1 : (dB == 2 * dA ? 2 : 0);
   const size_t cb = (size_t)n * L.H * L.W * L.CP * 2 * SP;
   if (!sB || cb >= 0xE0000000ull) return no;
+  // every dilation class of A holds a row: the lane walk and the A-in row cursor leave a clip
+  // after its class dA - 1, which a map of fewer than dA rows does not have -- from the second
+  // clip of a stream on they would step dA rows where the next class is one row away (wrong
+  // logits on 1 x 40 and 7 x 40 maps at 600 clips; such layers stay on block16w_kernel)
+  if (L.H < dA) return no;
   // bf16 with full 40-pixel rows: two streams per workgroup when both rings fit half the LDS
   const char* nse = getenv("HONK_PAIR_STREAMS");
   // (round 6: on the row-table walk, block16p_kernel<..., 2, 0, -1, -1>: its smaller per-wave
@@ -1663,7 +1668,9 @@ static PairPlan pair_at(const Layout& L, const honk_res_desc* d, int FM, int64_t
     // 40-pixel rows: the compile-time tap-step instances where their pad columns fit two
     // streams (res15's (1,1) (1,2) (2,2) (4,4) pairs; HONK_PAIR_IMM2=0 keeps the row table)
     const char* ie = getenv("HONK_PAIR_IMM2");
-    if (pair_imm(L, FM, dA, dB) && !(ie && ie[0] == '0')) {
+    // ((4,8) has no two-stream tap-step instance, launch_pair2i_vf: its pads fit two streams
+    // only on maps of a few rows, where the row table serves as well)
+    if (pair_imm(L, FM, dA, dB) && !(dA == 4 && dB == 8) && !(ie && ie[0] == '0')) {
       PairPlan pi = plan_pair(L, FM, dA, sB, (int)cdiv(cdiv(n, grid), 2), 2, true, true);
       pi.tbl = false;
       if (pi.ok && pi.ppr == 4 && pi.ppw <= pair_ppw(SP, pi.ppr)) return pi;

@@ -226,7 +226,9 @@ def linear(x, w, b):
 def res_forward(params, cfg, x, acc=np.float64, trace=None):
     """SpeechResModel.forward, model.py:104-121.
 
-    x: [B, 101, 40].  Returns logits [B, n_labels].
+    x: [B, H, W] -- any height and width the config's pool leaves a map of (101 x 40 is only
+    the reference's default input); nothing here may depend on the shape: the input-geometry
+    tests use this function as the oracle of every map size.  Returns logits [B, n_labels].
     trace: optional list receiving per-layer x after BN (pre-mean), for debugging.
     """
     x = np.asarray(x, dtype=acc)[:, None]                              # :105 unsqueeze(1)
