@@ -38,6 +38,7 @@
 #include "common.h"
 
 #include <cstring>
+#include <vector>
 
 namespace honk {
 namespace res {
@@ -637,8 +638,6 @@ __global__ __launch_bounds__(256) void tail_sum_live_kernel(const float* __restr
 #include "res_bf16r.inc"
 #include "res_bf16w.inc"
 #include "res_bf16p.inc"
-#include "res_bf16k.inc"
-#include "res_bf16n.inc"
 
 // conv0m / conv0p staging: the clip's [Hin][Win] fp32 map through put(r, c, v), 256 threads.
 // Rows of whole float4s: a thread's U loads all in flight before its first LDS write (res8 /
@@ -1338,7 +1337,37 @@ static int make_layout(const honk_res_desc* d, Layout* L) {
   return HONK_OK;
 }
 
-static int64_t chunk_clips(const Layout& L, int64_t batch) {
+// The environment of one call: read at the top of every C-ABI entry that plans, on every call
+// (callers flip the variables between calls), and handed down -- nothing below reads getenv.
+// A switch holds its variable's first character, 0 when unset.
+struct Switches {
+  char kernel;     // HONK_RES_KERNEL: w / r force a block kernel family, p the pair path
+  char last;       // HONK_LAST_KERNEL: w keeps the last layer on block16w_kernel
+  char streams;    // HONK_PAIR_STREAMS: 1 keeps the bf16 pairs on one stream
+  char lin;        // HONK_PAIR_LIN: 0 keeps the row pieces of the A-in DMA
+  char imm2;       // HONK_PAIR_IMM2: 0 keeps the two-stream pairs on the row table
+  char conv0;      // HONK_CONV0: v the VALU kernel, m conv0m_kernel where conv0p_kernel would run
+  char rerun;      // HONK_F16X2_RERUN: 0 turns the f16x2 admission off
+  bool has_chunk;  // HONK_RES_CHUNK is set: clips per chunk
+  int64_t chunk;
+  bool rerun_on() const { return rerun != '0'; }
+};
+static Switches read_switches() {
+  auto first = [](const char* name) {
+    const char* e = getenv(name);
+    return e ? e[0] : '\0';
+  };
+  Switches sw{first("HONK_RES_KERNEL"), first("HONK_LAST_KERNEL"), first("HONK_PAIR_STREAMS"),
+              first("HONK_PAIR_LIN"),   first("HONK_PAIR_IMM2"),   first("HONK_CONV0"),
+              first("HONK_F16X2_RERUN"), false, 0};
+  if (const char* e = getenv("HONK_RES_CHUNK")) {
+    sw.has_chunk = true;
+    sw.chunk = atoll(e);
+  }
+  return sw;
+}
+
+static int64_t chunk_clips(const Layout& L, const Switches& sw, int64_t batch) {
   const size_t per_clip = (size_t)L.H * L.W * L.CP * sizeof(float);
   // 4096 clips (3.2 GB per buffer for res15) keeps >200 tiles per CU per launch; pooled maps
   // (res8 25 x 13, res26 50 x 20: <= 256 KiB per clip) take 8192 -- a res8 chunk's six
@@ -1347,7 +1376,7 @@ static int64_t chunk_clips(const Layout& L, int64_t batch) {
   int64_t ch = per_clip <= ((size_t)256 << 10)   ? 8192
                : per_clip <= ((size_t)1 << 20) ? 4096
                                                : (int64_t)((size_t)4 << 30) / (int64_t)per_clip;
-  if (const char* e = getenv("HONK_RES_CHUNK")) ch = atoll(e);
+  if (sw.has_chunk) ch = sw.chunk;
   if (ch < 1) ch = 1;
   return batch < ch ? batch : ch;
 }
@@ -1457,22 +1486,31 @@ static int bands_w(const Layout& L, const honk_res_desc* d, int FM, int i) {
   const int th = plan_w_th(L, FM, dl);
   return th ? band_geo(L.H, dl, th).nbc : 0;
 }
-// Which bf16 / bf16x3 block kernel runs: the weight-stationary one where it was
-// measured faster (45 maps at bf16x3: res15 2.14 vs 2.21 ms per 4096-clip
-// launch; it loses 7-20 % on the narrow, pooled and bf16 configurations), the
-// row-band one elsewhere.  HONK_RES_KERNEL=w / r forces either (tests run both).
 struct PairPlan {
   bool ok;
   int lag, NRA, NRB, slotb, ppr, ppw;  // ppw: DMA pieces per A wave per step
   int padb;                            // f16x2: zero-column bytes each side of a slot's row
   int ns;                              // streams per workgroup (block16p_kernel NS)
   bool tbl;                            // bf16 two streams: the row-table instance (SCA = -1)
-  int ks;                              // 2: f16x2 with K split over two waves per SIMD (block16k_kernel)
   bool lin;                            // bf16 two streams, undilated A: linear A-in DMA (block16p_body LIN)
   int ringpad;                         // shared pad columns (Block16PArgs::ringpad)
 };
-static PairPlan pair_at(const Layout& L, const honk_res_desc* d, int FM, int64_t n, int grid, int i);
-static bool use_w_kernel(const Layout& L, const honk_res_desc* d, int FM) {
+static PairPlan pair_at(const Layout& L, const honk_res_desc* d, const Switches& sw, int FM, int64_t n, int grid,
+                        int i);
+
+// The kernel family a descriptor runs on, or why the 16-bit kernels refuse it.  Independent
+// of the batch and the CU count.  bf16 / bf16x3: the weight-stationary family (with its fused
+// pairs and last layer) where it was measured faster (45 maps at bf16x3: res15 2.14 vs 2.21
+// ms per 4096-clip launch; it loses 7-20 % on the narrow, pooled and bf16 configurations),
+// the row-band kernel elsewhere.  HONK_RES_KERNEL=w / r forces either (tests run both).
+enum Path {
+  PATH_F32,       // block_kernel
+  PATH_ROWBAND,   // block16r_kernel
+  PATH_WSTAT,     // block16w_kernel, block16p_kernel pairs, block16l_kernel
+  PATH_NO_WIDTH,  // refused: the width does not fit the row-band staging plan
+  PATH_NO_F16X2,  // refused: f16x2 outside the weight-stationary family's envelope
+};
+static bool use_w_kernel(const Layout& L, const honk_res_desc* d, const Switches& sw, int FM) {
   // 45-map bf16x3: the weight-stationary path (with fused pairs); bf16: only when
   // pairs fuse (the single weight-stationary layer is slower than the row-band one)
   // (measured: res15 bf16 +4 %; res8's 13-pixel rows lose 20 % -- row-band there);
@@ -1480,19 +1518,17 @@ static bool use_w_kernel(const Layout& L, const honk_res_desc* d, int FM) {
   // bf16 on rows < 32 pixels (res8, res26): only an even stack whose every layer pairs on
   // the two-stream kernel (every pair and the last one; measured res8 0.128 ms per pair
   // launch vs 2 x 0.070 row-band layers)
-  bool want = FM == 2 || (L.NT == 3 && (FM == 1 || (L.W >= 32 && L.L >= 3 && pair_at(L, d, FM, 4096, 256, 1).ok)));
+  bool want = FM == 2 || (L.NT == 3 && (FM == 1 || (L.W >= 32 && L.L >= 3 && pair_at(L, d, sw, FM, 4096, 256, 1).ok)));
   if (FM == 0 && L.NT == 3 && L.W < 32 && L.L >= 2 && L.L % 2 == 0) {
     bool all = true;
     for (int i = 1; i < L.L && all; i += 2) {
-      const PairPlan pp = pair_at(L, d, FM, 4096, 256, i);
+      const PairPlan pp = pair_at(L, d, sw, FM, 4096, 256, i);
       all = pp.ok && pp.ns == 2;
     }
     want = want || all;
   }
-  if (const char* e = getenv("HONK_RES_KERNEL")) {
-    if (e[0] == 'r' && FM != 2) return false;
-    if (e[0] == 'w' || e[0] == 'p') want = true;
-  }
+  if (sw.kernel == 'r' && FM != 2) return false;
+  if (sw.kernel == 'w' || sw.kernel == 'p') want = true;
   if (!want) return false;
   if (L.W >= 64) return false;  // m-tile walk steps 64 pixels = at most one row carry
   if (L.C >= L.CP) return false;  // no zero-padding channel for the folded bias
@@ -1501,13 +1537,29 @@ static bool use_w_kernel(const Layout& L, const honk_res_desc* d, int FM) {
     if (!bands_w(L, d, FM, i)) return false;
   return true;
 }
+static Path plan_path(const Layout& L, const honk_res_desc* d, const Switches& sw) {
+  if (L.prec == HONK_PREC_F32) return PATH_F32;
+  const int FM = fmt_of(L.prec);
+  if (plan_block16r(L, sp_of(FM)).TH == 0) return PATH_NO_WIDTH;
+  if (use_w_kernel(L, d, sw, FM)) return PATH_WSTAT;
+  return FM == 2 ? PATH_NO_F16X2 : PATH_ROWBAND;
+}
+// the refusals as the workspace query and the forward word them
+static int refuse_path(const Layout& L, Path path) {
+  if (path == PATH_NO_WIDTH)
+    return fail(HONK_ERR_UNSUPPORTED, "bf16/bf16x3: feature-map width %d exceeds the row-band staging plan "
+                "(use precision f32)", L.W);
+  return fail(HONK_ERR_UNSUPPORTED, "f16x2 runs on the weight-stationary / pair kernels only: %d maps, %dx%d "
+              "(pooled) map, pool %dx%d is outside their envelope (use precision f32 or bf16x3)", L.C, L.H, L.W,
+              L.ph, L.pw);
+}
 
 // Fused pair plan (res_bf16p.inc) for layers A (dilation d) and B (tap stride sB
 // class rows), at most `cpw` clips per workgroup: B's lag and the ring sizes from
 // an exact walk over the steps of the longest stream.  ok = false: does not fit.
 static PairPlan plan_pair(const Layout& L, int FM, int d, int sB, int cpw, int nstreams = 1, bool padcols = false,
-                          bool tbl = false, int ks = 1, bool lin = false, bool sharedpad = false) {
-  PairPlan pp{false, 0, 0, 0, 0, 0, 0, 0, nstreams, tbl, ks, lin, 0};
+                          bool tbl = false, bool lin = false, bool sharedpad = false) {
+  PairPlan pp{false, 0, 0, 0, 0, 0, 0, 0, nstreams, tbl, lin, 0};
   const int SP = sp_of(FM);
   const int P = 64, W = L.W, H = L.H;
   const long PXB = g16p_pxb(L.NT, SP);  // LDS pixel pitch
@@ -1606,8 +1658,7 @@ static PairPlan plan_pair(const Layout& L, int FM, int d, int sB, int cpw, int n
     if ((long)pp.NRA * pp.slotb / 1024 <= 2 * pp.ppw + pieces(-1)) return pp;  // (the ring must outrun a step)
   }
   pp.NRB = (int)(nrb > 2 ? nrb : 2);
-  const long extra = ks == 2 ? g16p_lds_extra(true, 8, pp.slotb) + g16k_xch_bytes()
-                             : g16p_lds_extra(FM == 2 || padcols || tbl, 4, pp.slotb);
+  const long extra = g16p_lds_extra(FM == 2 || padcols || tbl, 4, pp.slotb);
   if (tbl && nstreams > 1)  // the streams share the zero block, sink and zeroed slot (block16p_body SHZ)
     pp.ok = (long)(pp.NRA + pp.NRB) * pp.slotb + pp.ringpad + 4 * g16p_tr() * g16p_teb() <=
             g16p_stream_bytes(nstreams, pp.slotb + pp.ringpad);
@@ -1633,11 +1684,11 @@ static bool pair_imm(const Layout& L, int FM, int dA, int dB) {
   return (dA == 1 && (dB == 1 || dB == 2)) || (dA == 2 && dB == 2) || (dA == 4 && (dB == 4 || dB == 8)) ||
          (dA == 8 && dB == 8);
 }
-static PairPlan pair_at(const Layout& L, const honk_res_desc* d, int FM, int64_t n, int grid, int i) {
-  const PairPlan no{false, 0, 0, 0, 0, 0, 0, 0, 1, false, 1};
+static PairPlan pair_at(const Layout& L, const honk_res_desc* d, const Switches& sw, int FM, int64_t n, int grid,
+                        int i) {
+  const PairPlan no{false, 0, 0, 0, 0, 0, 0, 0, 1, false, false, 0};
   const int SP = sp_of(FM);
-  const char* kenv = getenv("HONK_RES_KERNEL");
-  if (L.NT != 3 || (kenv && (kenv[0] == 'w' || kenv[0] == 'r'))) return no;
+  if (L.NT != 3 || sw.kernel == 'w' || sw.kernel == 'r') return no;
   // (bf16: B may be an even last layer -- it stores its output like any pair and
   // tail_act_kernel sums it; the other formats keep their fused last-layer sums)
   if (i % 2 == 0 || i + 1 > L.L || (i + 1 == L.L && FM != 0)) return no;
@@ -1651,31 +1702,28 @@ static PairPlan pair_at(const Layout& L, const honk_res_desc* d, int FM, int64_t
   // logits on 1 x 40 and 7 x 40 maps at 600 clips; such layers stay on block16w_kernel)
   if (L.H < dA) return no;
   // bf16 with full 40-pixel rows: two streams per workgroup when both rings fit half the LDS
-  const char* nse = getenv("HONK_PAIR_STREAMS");
   // (round 6: on the row-table walk, block16p_kernel<..., 2, 0, -1, -1>: its smaller per-wave
   // state fits 256 registers with 32 weight fragments pinned and no spill -- res15 bf16 408K
   // -> 469K clips/s against the walk-based two-stream kernel (19 spilled values reloaded in
   // its step loop, now removed), 416K with one stream on the tap-step instances, same box;
   // HONK_PAIR_STREAMS=1 selects those)
-  if (FM == 0 && !(nse && nse[0] == '1')) {
+  if (FM == 0 && sw.streams != '1') {
     // undilated A on narrow rows whose LDS pixel is the HBM pixel: the linear A-in DMA
     // (HONK_PAIR_LIN=0 keeps the row pieces)
-    const char* le = getenv("HONK_PAIR_LIN");
-    if (dA == 1 && g16p_pxb(3, SP) == 32 * 3 * SP && L.W < 32 && !(le && le[0] == '0')) {
-      const PairPlan pl = plan_pair(L, FM, dA, sB, (int)cdiv(cdiv(n, grid), 2), 2, false, true, 1, true);
+    if (dA == 1 && g16p_pxb(3, SP) == 32 * 3 * SP && L.W < 32 && sw.lin != '0') {
+      const PairPlan pl = plan_pair(L, FM, dA, sB, (int)cdiv(cdiv(n, grid), 2), 2, false, true, true);
       if (pl.ok && pl.ppr == 2 && pl.ppw <= 4) return pl;
     }
     // 40-pixel rows: the compile-time tap-step instances where their pad columns fit two
     // streams (res15's (1,1) (1,2) (2,2) (4,4) pairs; HONK_PAIR_IMM2=0 keeps the row table)
-    const char* ie = getenv("HONK_PAIR_IMM2");
     // ((4,8) has no two-stream tap-step instance, launch_pair2i_vf: its pads fit two streams
     // only on maps of a few rows, where the row table serves as well)
-    if (pair_imm(L, FM, dA, dB) && !(dA == 4 && dB == 8) && !(ie && ie[0] == '0')) {
+    if (pair_imm(L, FM, dA, dB) && !(dA == 4 && dB == 8) && sw.imm2 != '0') {
       PairPlan pi = plan_pair(L, FM, dA, sB, (int)cdiv(cdiv(n, grid), 2), 2, true, true);
       pi.tbl = false;
       if (pi.ok && pi.ppr == 4 && pi.ppw <= pair_ppw(SP, pi.ppr)) return pi;
       // the pads shared between neighbouring slots (one pad per slot): (8,8) then fits
-      pi = plan_pair(L, FM, dA, sB, (int)cdiv(cdiv(n, grid), 2), 2, true, true, 1, false, true);
+      pi = plan_pair(L, FM, dA, sB, (int)cdiv(cdiv(n, grid), 2), 2, true, true, false, true);
       pi.tbl = false;
       if (pi.ok && pi.ringpad > 0 && pi.ppr == 4 && pi.ppw <= pair_ppw(SP, pi.ppr)) return pi;
     }
@@ -1683,14 +1731,6 @@ static PairPlan pair_at(const Layout& L, const honk_res_desc* d, int FM, int64_t
     if (p2.ok && (p2.ppr == 4 || p2.ppr == 2) && p2.ppw <= pair_ppw(SP, p2.ppr)) return p2;
   }
   const bool imm = pair_imm(L, FM, dA, dB);
-  const int ppw = pair_ppw(SP, imm ? 4 : 0);
-  if (FM == 2 && imm && getenv("HONK_PAIR_KS") && getenv("HONK_PAIR_KS")[0] == '1') {
-    // opt-in: the K split over two waves per SIMD (block16k_kernel, res_bf16k.inc) -- measured
-    // 4-5 % slower than the one-wave pair (res15 f16x2 312K vs 327K clips/s, same box;
-    // DESIGN.md §3), so the default stays block16p_kernel
-    const PairPlan pk = plan_pair(L, FM, dA, sB, (int)cdiv(n, grid), 1, true, false, 2);
-    if (pk.ok && pk.ppr == 4 && pk.ppw <= ppw) return pk;
-  }
   const PairPlan pp = plan_pair(L, FM, dA, sB, (int)cdiv(n, grid), 1, imm);
   const int ppw1 = pair_ppw(SP, pp.ppr);
   return pp.ok && ppw1 && pp.ppw <= ppw1 ? pp : no;
@@ -1702,12 +1742,10 @@ static PairPlan pair_at(const Layout& L, const honk_res_desc* d, int FM, int64_t
 // stream's share of the LDS.  One clip per stream pass: the plan of a 1-clip stream
 // (no A-out ring: NRB = 1 unused slot, no lag).  HONK_LAST_KERNEL=w keeps the
 // weight-stationary kernel (the pair-vs-w bitwise tests).
-static PairPlan last_at(const Layout& L, const honk_res_desc* d, int FM, int i) {
-  const PairPlan no{false, 0, 0, 0, 0, 0, 0, 0, 1, false, 1};
+static PairPlan last_at(const Layout& L, const honk_res_desc* d, const Switches& sw, int FM, int i) {
+  const PairPlan no{false, 0, 0, 0, 0, 0, 0, 0, 1, false, false, 0};
   const int SP = sp_of(FM);
-  const char* kenv = getenv("HONK_RES_KERNEL");
-  const char* lenv = getenv("HONK_LAST_KERNEL");
-  if (L.NT != 3 || (kenv && (kenv[0] == 'w' || kenv[0] == 'r')) || (lenv && lenv[0] == 'w')) return no;
+  if (L.NT != 3 || sw.kernel == 'w' || sw.kernel == 'r' || sw.last == 'w') return no;
   if (i != L.L || i % 2 == 0 || L.W != 40) return no;
   // two streams of 2 A waves: one wave per SIMD (bf16 with four streams, two waves per
   // SIMD at 256 registers, spilled the weights: 3.38 vs 1.65 ms per 4096-clip launch)
@@ -1829,12 +1867,11 @@ static int launch_conv0(const Layout& L, const float* x, OT* out, const float* w
 // else the VALU kernel.  HONK_CONV0=v forces the VALU kernel (A/B experiments).
 template <int NT, int FM, bool ONES>
 static int launch_conv0m_nt(const Layout& L, const float* x, void* out, const float* w0, int64_t n,
-                            hipStream_t st, const float* cscale, LiveRef live) {
+                            hipStream_t st, const float* cscale, LiveRef live, char conv0) {
   const unsigned lds = 2u * (unsigned)((L.Hin + 2) * (L.Win + 2)) * 2u;
   // bf16 with a pool: the shared-layout patch kernel (conv0p_kernel); HONK_CONV0=m keeps conv0m_kernel
-  const char* ce = getenv("HONK_CONV0");
   if constexpr (FM == 0) {
-    if (L.ph * L.pw > 1 && !(ce && ce[0] == 'm')) {
+    if (L.ph * L.pw > 1 && conv0 != 'm') {
       const unsigned ldsp = lds + 2u * (unsigned)(L.Win + 2);
 #define HONK_C0P(ph_, pw_)                                                                                     \
   if (L.ph == ph_ && L.pw == pw_) {                                                                            \
@@ -1873,17 +1910,16 @@ static int launch_conv0m_nt(const Layout& L, const float* x, void* out, const fl
   return 1;  // no instance
 }
 template <int FM, bool ONES>
-// live (FM 1 only): the launch's clips that run come from the device (LiveRef)
+// live (FM 1 only): the launch's clips that run come from the device (LiveRef); conv0: Switches::conv0
 static int launch_conv0_16(const Layout& L, const float* x, void* out, const float* w0, int64_t n, hipStream_t st,
-                           const float* cscale = nullptr, LiveRef live = LiveRef{nullptr, 0, 0}) {
-  const char* e = getenv("HONK_CONV0");
-  const bool valu = e && e[0] == 'v';
+                           const float* cscale, LiveRef live, char conv0) {
+  const bool valu = conv0 == 'v';
   const bool fits = 2L * (L.Hin + 3) * (L.Win + 2) * 2 <= 160 * 1024 && n <= 0x7fffffff;
   if (!valu && fits) {
     int rc = 1;
-    if (L.NT == 1) rc = launch_conv0m_nt<1, FM, ONES>(L, x, out, w0, n, st, cscale, live);
-    else if (L.NT == 2) rc = launch_conv0m_nt<2, FM, ONES>(L, x, out, w0, n, st, cscale, live);
-    else if (L.NT == 3) rc = launch_conv0m_nt<3, FM, ONES>(L, x, out, w0, n, st, cscale, live);
+    if (L.NT == 1) rc = launch_conv0m_nt<1, FM, ONES>(L, x, out, w0, n, st, cscale, live, conv0);
+    else if (L.NT == 2) rc = launch_conv0m_nt<2, FM, ONES>(L, x, out, w0, n, st, cscale, live, conv0);
+    else if (L.NT == 3) rc = launch_conv0m_nt<3, FM, ONES>(L, x, out, w0, n, st, cscale, live, conv0);
     if (rc <= 0) return rc;
   }
   if (live.count) return fail(HONK_ERR_UNSUPPORTED, "the stream-ordered re-run needs the matrix-core conv0 kernel");
@@ -1891,300 +1927,265 @@ static int launch_conv0_16(const Layout& L, const float* x, void* out, const flo
   else return launch_conv0<__bf16, FM == 1, ONES>(L, x, (__bf16*)out, w0, n, st);
 }
 
-// the whole-stack kernel (res_bf16n.inc) takes the model: bf16, every layer at
-// dilation 1, a zero-padding channel for the folded bias, 2 or 3 out-tiles, a map
-// whose image fits its LDS slot, at least one m-tile per wave.  Opt-in
-// (HONK_RES_KERNEL=n): on res8 it measured 0.50 ms per 4096-clip launch against the
-// row-band kernel's 0.45 ms for the same six layers, so the default stays.
-static bool use_n_kernel(const Layout& L, const honk_res_desc* d, int FM) {
-  const char* e = getenv("HONK_RES_KERNEL");
-  if (!e || e[0] != 'n') return false;
-  if (FM != 0 || L.L < 1 || L.C >= L.CP || (L.NT != 2 && L.NT != 3)) return false;
-  for (int i = 1; i <= L.L; ++i)
-    if (dil_of(d, i) != 1) return false;
-  if (!g16n_fits(L.NT, L.H, L.W)) return false;
-  return (L.H * L.W + 15) / 16 >= 4;
+// The launches of one chunk's block layers, in order: the one statement of which kernel runs
+// which layer.  honk_res_launch_plan reports it and the forward runs it.  A step is one
+// launch: its kind (HONK_KERNEL_*), its first layer (1-based; a pair covers layer and
+// layer + 1) and what that launch needs.
+struct Step {
+  int kind, layer;
+  PairPlan pp;  // HONK_KERNEL_PAIR, HONK_KERNEL_LAST
+  int TH;       // HONK_KERNEL_WSTAT, HONK_KERNEL_ROWBAND: the band height and its geometry
+  BandGeo bg;
+};
+struct Schedule {
+  int64_t n;  // planned for chunks of n clips on grid workgroups (0: not planned yet)
+  int grid;
+  Path path;
+  std::vector<Step> steps;
+  Plan p32;          // PATH_F32: block_kernel's plan, every layer's
+  PlanR pr;          // PATH_ROWBAND: block16r_kernel's
+  int parts_last;    // channel-sum partials per clip the last layer leaves the tail
+  bool last_stored;  // the last layer ran as a pair's B layer and stored its output (tail_act_kernel)
+};
+// (path = plan_path(L, d, sw): it depends on neither n nor grid, so a call decides it once)
+static Schedule plan_chunk(const Layout& L, const honk_res_desc* d, const Switches& sw, Path path, int64_t n,
+                           int grid) {
+  Schedule s{n, grid, path, {}, Plan{}, PlanR{}, 0, false};
+  const int FM = fmt_of(L.prec);
+  auto band_step = [&](int kind, int i, int TH) {  // returns the layer's bands per clip
+    s.steps.push_back(Step{kind, i, PairPlan{}, TH, band_geo(L.H, dil_of(d, i), TH)});
+    return s.steps.back().bg.nbc;
+  };
+  if (s.path == PATH_F32) {
+    s.p32 = plan_block(L);
+    for (int i = 1; i <= L.L; ++i) s.steps.push_back(Step{HONK_KERNEL_BLOCK_F32, i, PairPlan{}, s.p32.TH, BandGeo{}});
+    s.parts_last = s.p32.nbands * MW;
+  } else if (s.path == PATH_ROWBAND) {
+    s.pr = plan_block16r(L, sp_of(FM));
+    for (int i = 1; i <= L.L; ++i) s.parts_last = band_step(HONK_KERNEL_ROWBAND, i, s.pr.TH) * 8 * s.pr.MT;
+  } else if (s.path == PATH_WSTAT) {
+    // tiles of the weight-stationary layers = (clip, dilation class, band of TH class rows), TH per dilation
+    for (int i = 1; i <= L.L; ++i) {
+      PairPlan pp = pair_at(L, d, sw, FM, n, grid, i);
+      if (pp.ok) {
+        s.steps.push_back(Step{HONK_KERNEL_PAIR, i, pp, 0, BandGeo{}});
+        if (++i == L.L) s.last_stored = true;  // layer i + 1 done too
+        continue;
+      }
+      pp = last_at(L, d, sw, FM, i);
+      if (pp.ok) {
+        s.steps.push_back(Step{HONK_KERNEL_LAST, i, pp, 0, BandGeo{}});
+        s.parts_last = 2;
+        continue;
+      }
+      const int nbc = band_step(HONK_KERNEL_WSTAT, i, plan_w_th(L, FM, dil_of(d, i)));
+      if (i == L.L) s.parts_last = nbc * 4;
+    }
+  }
+  return s;
 }
 
-template <int NT>
-static int launch_block16n(const Layout& L, const __bf16* in, const float* frb, size_t frl, float* chsum, int64_t n,
-                           hipStream_t st) {
-  Block16NArgs a;
-  a.in = in;
-  a.wfrag = (const char*)frb;
-  a.wstride = (int)(frl * sizeof(float));
-  a.chsum = chsum;
-  a.nclips = (int)n;
-  a.H = L.H;
-  a.W = L.W;
-  a.nL = L.L;
-  int grid = cu_count();
-  if (grid > n) grid = (int)n;
-  TimedLaunch tl(st, 2.0 * L.H * L.W * L.C * L.C * 9 * L.L * (double)n);
-  hipLaunchKernelGGL((block16n_kernel<NT>), dim3(grid), dim3(256), 0, st, a);
-  HONK_LAUNCH_CHECK("res block16n_kernel");
-  tl.done(st);
-  return HONK_OK;
-}
-
-// bf16 driver: same schedule as the fp32 one (R / X0 / X1 buffers, fused mean)
-// bf16 schedule: activations stay pre-BN (see res_bf16.inc), so one residual
-// stream R (conv0 output, then every even layer's sum, in place) and one odd-layer
-// buffer X suffice; each layer writes exactly one tensor.
 // res_vf.hip (compiled with its own flags): the pair and last-layer launches
 bool launch_pair_vf(int FM, int ppr, bool imm, int dA, int dB, dim3 gd, dim3 bd, hipStream_t st,
                     const Block16PArgs& pa);
 void launch_last_vf(int FM, int d, dim3 gd, dim3 bd, hipStream_t st, const Block16PArgs& pa);
 void launch_pair2t_vf(int ppr, bool lin, dim3 gd, dim3 bd, hipStream_t st, const Block16PArgs& pa);
 bool launch_pair2i_vf(int dA, int dB, dim3 gd, dim3 bd, hipStream_t st, const Block16PArgs& pa);
-bool launch_pairk_vf(int dA, int dB, dim3 gd, dim3 bd, hipStream_t st, const Block16PArgs& pa);
 
+// What the 16-bit launches of one chunk share.  Activations stay pre-BN (see res_bf16.inc), so
+// one residual stream R (conv0's output, then every even layer's sum, in place) and one
+// odd-layer buffer X suffice; each layer writes exactly one tensor.
+struct Chunk16 {
+  const Layout& L;
+  const honk_res_desc* d;
+  const float* packed;
+  int FM, SP;  // operand format (res_bf16w.inc), 16-bit elements per channel value
+  __bf16 *R, *X;
+  float* chsum;
+  const float* frb;  // this format's packed weight fragments, frl floats per layer
+  size_t frl;
+  hipStream_t st;
+  LiveRef live;
+  int64_t n;  // the chunk's clips, on grid workgroups
+  int grid;
+  double layer_flop() const { return 2.0 * L.H * L.W * L.C * L.C * 9 * (double)n; }
+};
+
+// a fused pair (layers i, i + 1) or the last layer on the pair machinery (layer A only)
+static int run_pair(const Chunk16& c, const Step& s) {
+  const Layout& L = c.L;
+  const PairPlan& pp = s.pp;
+  const bool last = s.kind == HONK_KERNEL_LAST;
+  const int i = s.layer, dA = dil_of(c.d, i), dB = last ? dA : dil_of(c.d, i + 1);
+  Block16PArgs pa;
+  pa.R = c.R;  // (the last layer is odd: it reads R)
+  pa.chsum = last ? c.chsum : nullptr;
+  pa.wA = (const char*)(c.frb + (size_t)(i - 1) * c.frl);
+  pa.wB = last ? pa.wA : (const char*)(c.frb + (size_t)i * c.frl);
+  pa.chunk_bytes = (unsigned)((size_t)c.n * L.H * L.W * L.CP * 2 * c.SP);
+  pa.nclips = (int)c.n;
+  pa.H = L.H;
+  pa.W = L.W;
+  pa.d = dA;
+  pa.lgd = 0;
+  while ((1 << pa.lgd) < dA) ++pa.lgd;
+  pa.sB = dB == dA ? 1 : 2;
+  pa.lag = pp.lag;
+  pa.NRA = pp.NRA;
+  pa.NRB = pp.NRB;
+  pa.slotb = pp.slotb;
+  pa.ppr = pp.ppr;
+  pa.padb = pp.padb;
+  pa.ringpad = pp.ringpad;
+  pa.live = c.live;
+  if (last) {
+    TimedLaunch tl(c.st, c.layer_flop());
+    launch_last_vf(c.FM, dA, dim3(c.grid), dim3(128 * pp.ns), c.st, pa);
+    HONK_LAUNCH_CHECK("res block16l_kernel");
+    tl.done(c.st);
+    return HONK_OK;
+  }
+  TimedLaunch tl(c.st, 2.0 * c.layer_flop());
+  const dim3 gd(c.grid), bd(256 * pp.ns);
+  if (c.FM == 0 && pp.ns == 2 && pp.padb > 0) {
+    if (!launch_pair2i_vf(dA, dB, gd, bd, c.st, pa))
+      return fail(HONK_ERR_UNSUPPORTED, "block16p: no two-stream tap-step instance for dilations %d, %d", dA, dB);
+  } else if (c.FM == 0 && pp.ns == 2) launch_pair2t_vf(pp.ppr, pp.lin, gd, bd, c.st, pa);
+  else if (!launch_pair_vf(c.FM, pp.ppr, pp.ppr == 4 && pp.padb > 0, dA, dB, gd, bd, c.st, pa))
+    return fail(HONK_ERR_UNSUPPORTED, "block16p: no tap-step instance for dilations %d, %d", dA, dB);
+  HONK_LAUNCH_CHECK("res block16p_kernel");
+  tl.done(c.st);
+  return HONK_OK;
+}
+
+// the fields Block16WArgs and Block16RArgs share: buffers by layer parity, band geometry, tiles
+template <typename Args>
+static int fill_band(const Chunk16& c, const Step& s, Args* a) {
+  const Layout& L = c.L;
+  const bool even = (s.layer % 2) == 0, last = s.layer == L.L;
+  a->in = even ? c.X : c.R;
+  a->res = even ? c.R : nullptr;
+  a->out = last ? nullptr : (even ? c.R : c.X);
+  a->chsum = last ? c.chsum : nullptr;
+  a->H = L.H;
+  a->W = L.W;
+  a->dil = dil_of(c.d, s.layer);
+  a->TH = s.TH;
+  a->nbc = s.bg.nbc;
+  a->rem = s.bg.rem;
+  a->nb1 = s.bg.nb1;
+  a->nb0 = s.bg.nb0;
+  if ((int64_t)c.n * a->nbc > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
+  a->ntiles = (int)(c.n * a->nbc);
+  a->live = c.live;
+  return HONK_OK;
+}
+static int run_wstat(const Chunk16& c, const Step& s) {
+  Block16WArgs a;
+  int rc = fill_band(c, s, &a);
+  if (rc) return rc;
+  a.wfrag = (const char*)(c.frb + (size_t)(s.layer - 1) * c.frl);
+  a.lgd = 0;
+  while ((1 << a.lgd) < a.dil) ++a.lgd;
+  TimedLaunch tl(c.st, c.layer_flop());
+  rc = dispatch_block16w(c.L.NT, c.FM, a, c.st);
+  tl.done(c.st);
+  return rc;
+}
+static int run_rowband(const Chunk16& c, const Step& s, const PlanR& pr) {
+  Block16RArgs a;
+  int rc = fill_band(c, s, &a);
+  if (rc) return rc;
+  a.bfrag = (const uint4*)(c.frb + (size_t)(s.layer - 1) * c.frl);
+  a.bias = c.packed + c.L.off_bias16 + (size_t)16 * c.L.CP * (s.layer - 1);
+  TimedLaunch tl(c.st, c.layer_flop());
+  rc = dispatch_block16r(pr, c.SP, a, c.st);
+  tl.done(c.st);
+  return rc;
+}
+
+// the head of a chunk: from the stored last layer (bf16, a pair's B layer), else from the last
+// layer's channel-sum partials; cscale, flags: f16x2 only (else null)
+static int run_tail16(const Chunk16& c, const Schedule& s, float* logits, const float* cscale, int* flags) {
+  const Layout& L = c.L;
+  const float* bn_last = c.packed + L.off_bn + (size_t)2 * L.CP * (L.L - 1);
+  const float *wout = c.packed + L.off_wout, *bout = c.packed + L.off_bout;
+  const bool w = s.path == PATH_WSTAT;
+  if (s.last_stored) {
+    if (L.CP != 48 || c.SP != 1) return fail(HONK_ERR_UNSUPPORTED, "tail_act_kernel: 48 bf16 channels only");
+    hipLaunchKernelGGL(tail_act_kernel, dim3((unsigned)c.n), dim3(256), 0, c.st, c.R, wout, bout, logits, L.H * L.W,
+                       L.C, L.NL, bn_last, bn_last + L.CP);
+    HONK_LAUNCH_CHECK("res tail_act_kernel");
+  } else if (c.live.count) {
+    hipLaunchKernelGGL(tail_sum_live_kernel, dim3((unsigned)c.n), dim3(256), 0, c.st, c.chsum, wout, bout, logits,
+                       s.parts_last, L.H * L.W, L.C, L.CP, L.NL, bn_last, bn_last + L.CP, c.live);
+    HONK_LAUNCH_CHECK(w ? "res tail_sum_live_kernel (weight-stationary)" : "res tail_sum_live_kernel (bf16 row-band)");
+  } else {
+    hipLaunchKernelGGL(tail_sum_kernel, dim3((unsigned)c.n), dim3(256), 0, c.st, c.chsum, wout, bout, logits,
+                       s.parts_last, L.H * L.W, L.C, L.CP, L.NL, bn_last, bn_last + L.CP, cscale,
+                       c.packed + L.off_range + HONK_NUM_OUT_SCALE, flags, w ? (float)HONK_F16X2_Z_MAX : 0.f);
+    HONK_LAUNCH_CHECK(w ? "res tail_sum_kernel (weight-stationary)" : "res tail_sum_kernel (bf16 row-band)");
+  }
+  return HONK_OK;
+}
+
+// The 16-bit forward: per chunk, the clip scales (f16x2), conv0, the schedule's steps, the head.
+// sch: the caller's schedule (and path), planned here once per chunk size (a call has at most
+// two: the full chunk and the remainder) and kept across the calls of the re-run rounds
 // flags (f16x2 only, may be null): [batch] the clips' admission flags (clip_scale_kernel,
 // tail_sum_kernel; honk_res_forward re-runs the flagged clips)
 // live (bf16x3 only, count may be null; batch <= chunk): every kernel runs the first
 // live_clips() clips of the batch it is launched for (honk_res_forward_ordered's re-run rounds)
-static int forward_bf16(const Layout& L, const honk_res_desc* d, const float* packed, const float* x,
-                        float* logits, int64_t batch, int64_t chunk, void* workspace, hipStream_t st,
-                        int* flags = nullptr, LiveRef live = LiveRef{nullptr, 0, 0}) {
-  const int FM = fmt_of(L.prec);  // operand format (res_bf16w.inc)
-  if (live.count && (FM != 1 || batch > chunk || use_n_kernel(L, d, FM)))
+static int forward_bf16(const Layout& L, const honk_res_desc* d, const Switches& sw, Schedule* sch,
+                        const float* packed, const float* x, float* logits, int64_t batch, int64_t chunk,
+                        void* workspace, hipStream_t st, int* flags = nullptr,
+                        LiveRef live = LiveRef{nullptr, 0, 0}) {
+  const int FM = fmt_of(L.prec), SP = sp_of(FM);
+  if (live.count && (FM != 1 || batch > chunk))
     return fail(HONK_ERR_UNSUPPORTED, "a device-held clip count: bf16x3, one chunk");
-  const int SP = sp_of(FM);       // 16-bit elements per channel value
-  const size_t act = (size_t)chunk * L.H * L.W * L.CP * SP;
-  // this format's packed weight fragments (per layer)
-  const float* frb = FM == 1 ? packed + L.off_fragx3 : FM == 2 ? packed + L.off_fragh : packed + L.off_frag16;
-  const size_t frl = FM == 0 ? L.frag16_floats : L.fragx3_floats;
-  __bf16* R = (__bf16*)workspace;
-  __bf16* X = R + act;
-  float* cscale = (float*)(R + 2 * act);  // [chunk] the f16x2 clip scales (clip_scale_kernel)
-  float* chsum = cscale + round64((size_t)chunk);
-  const float* tail_cs = FM == 2 ? cscale : nullptr;
-  const PlanR pr = plan_block16r(L, SP);
-  const double layer_flop_per_clip = 2.0 * L.H * L.W * L.C * L.C * 9;
   if (L.L == 0) return fail(HONK_ERR_UNSUPPORTED, "bf16 path needs n_layers >= 1");
-  if (pr.TH == 0)
-    return fail(HONK_ERR_UNSUPPORTED, "bf16/bf16x3: feature-map width %d exceeds the row-band staging plan "
-                "(use precision f32)", L.W);
-  int rc;
-  if (use_n_kernel(L, d, FM)) {
-    // conv0 -> R, then the whole block stack per clip in LDS, then the head
-    for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
-      const int64_t n = (batch - c0 < chunk) ? batch - c0 : chunk;
-      rc = launch_conv0_16<0, true>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st);
-      if (rc) return rc;
-      rc = L.NT == 3 ? launch_block16n<3>(L, R, frb, frl, chsum, n, st) : launch_block16n<2>(L, R, frb, frl, chsum, n, st);
-      if (rc) return rc;
-      const float* bn_last = packed + L.off_bn + (size_t)2 * L.CP * (L.L - 1);
-      hipLaunchKernelGGL(tail_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
-                         packed + L.off_bout, logits + c0 * L.NL, 4, L.H * L.W, L.C, L.CP, L.NL, bn_last,
-                         bn_last + L.CP, tail_cs, packed + L.off_range + HONK_NUM_OUT_SCALE, (int*)nullptr, 0.f);
-      HONK_LAUNCH_CHECK("res tail_sum_kernel (whole stack)");
+  const size_t act = (size_t)chunk * L.H * L.W * L.CP * SP;
+  __bf16* R = (__bf16*)workspace;
+  float* cscale = (float*)(R + 2 * act);  // [chunk] the f16x2 clip scales (clip_scale_kernel)
+  const float* tail_cs = FM == 2 ? cscale : nullptr;
+  Chunk16 c{L, d, packed, FM, SP, R, R + act, cscale + round64((size_t)chunk),
+            FM == 1 ? packed + L.off_fragx3 : FM == 2 ? packed + L.off_fragh : packed + L.off_frag16,
+            FM == 0 ? L.frag16_floats : L.fragx3_floats, st, live, 0, 0};
+  const float* w0 = packed + L.off_conv0;
+  const Path path = sch->n ? sch->path : plan_path(L, d, sw);
+  if (path != PATH_WSTAT && path != PATH_ROWBAND) return refuse_path(L, path);
+  for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
+    c.n = (batch - c0 < chunk) ? batch - c0 : chunk;
+    c.grid = cu_count();
+    if (c.grid > c.n) c.grid = (int)c.n;
+    const float* xc = x + c0 * L.Hin * L.Win;
+    if (FM == 2) {
+      hipLaunchKernelGGL(clip_scale_kernel, dim3((unsigned)cdiv(c.n, 4)), dim3(256), 0, st, xc, packed + L.off_range,
+                         cscale, (int)c.n, L.Hin * L.Win, flags ? flags + c0 : nullptr);
+      HONK_LAUNCH_CHECK("res clip_scale_kernel");
     }
-    return HONK_OK;
-  }
-  const bool wpath = use_w_kernel(L, d, FM);
-  if (!wpath && FM == 2)
-    return fail(HONK_ERR_UNSUPPORTED, "f16x2 runs on the weight-stationary / pair kernels only: %d maps, %dx%d "
-                "(pooled) map, pool %dx%d is outside their envelope (use precision f32 or bf16x3)", L.C, L.H, L.W,
-                L.ph, L.pw);
-  if (wpath) {
-    // weight-stationary kernel: tiles = (clip, dilation class, band of TH class rows), TH per dilation
-    int parts_last = 0;  // channel-sum partials per clip of the last layer
-    for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
-      const int64_t n = (batch - c0 < chunk) ? batch - c0 : chunk;
-      if (FM == 2) {
-        hipLaunchKernelGGL(clip_scale_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, x + c0 * L.Hin * L.Win,
-                           packed + L.off_range, cscale, (int)n, L.Hin * L.Win, flags ? flags + c0 : nullptr);
-        HONK_LAUNCH_CHECK("res clip_scale_kernel");
-      }
-      rc = (FM == 1) ? launch_conv0_16<1, true>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st, nullptr,
-                                                live)
-           : (FM == 2) ? launch_conv0_16<2, true>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st, cscale)
-                       : launch_conv0_16<0, true>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st);
+    // (the weight-stationary family takes its folded bias from a channel of ones)
+    int rc;
+    if (path == PATH_WSTAT)
+      rc = FM == 1   ? launch_conv0_16<1, true>(L, xc, R, w0, c.n, st, nullptr, live, sw.conv0)
+           : FM == 2 ? launch_conv0_16<2, true>(L, xc, R, w0, c.n, st, cscale, live, sw.conv0)
+                     : launch_conv0_16<0, true>(L, xc, R, w0, c.n, st, nullptr, live, sw.conv0);
+    else
+      rc = FM == 1 ? launch_conv0_16<1, false>(L, xc, R, w0, c.n, st, nullptr, live, sw.conv0)
+                   : launch_conv0_16<0, false>(L, xc, R, w0, c.n, st, nullptr, live, sw.conv0);
+    if (rc) return rc;
+    // (planned with conv0 enqueued: a small batch's planning runs under it, not ahead of the first launch)
+    if (sch->n != c.n || sch->grid != c.grid) *sch = plan_chunk(L, d, sw, path, c.n, c.grid);
+    for (const Step& s : sch->steps) {
+      rc = s.kind == HONK_KERNEL_WSTAT     ? run_wstat(c, s)
+           : s.kind == HONK_KERNEL_ROWBAND ? run_rowband(c, s, sch->pr)
+                                           : run_pair(c, s);
       if (rc) return rc;
-      int grid = cu_count();
-      if (grid > n) grid = (int)n;
-      bool last_stored = false;  // the last layer ran as a pair's B layer (tail_act_kernel sums it)
-      for (int i = 1; i <= L.L; ++i) {
-        const bool even = (i % 2) == 0;
-        {
-          const PairPlan pp = pair_at(L, d, FM, n, grid, i);
-          if (pp.ok) {
-            if (i + 1 == L.L) last_stored = true;
-            const int dA = dil_of(d, i);
-            const size_t cb = (size_t)n * L.H * L.W * L.CP * 2 * SP;
-            Block16PArgs pa;
-            pa.R = R;
-            pa.chsum = nullptr;
-            pa.wA = (const char*)(frb + (size_t)(i - 1) * frl);
-            pa.wB = (const char*)(frb + (size_t)i * frl);
-            pa.chunk_bytes = (unsigned)cb;
-            pa.nclips = (int)n;
-            pa.H = L.H;
-            pa.W = L.W;
-            pa.d = dA;
-            pa.lgd = 0;
-            while ((1 << pa.lgd) < dA) ++pa.lgd;
-            pa.sB = dil_of(d, i + 1) == dA ? 1 : 2;
-            pa.lag = pp.lag;
-            pa.NRA = pp.NRA;
-            pa.NRB = pp.NRB;
-            pa.slotb = pp.slotb;
-            pa.ppr = pp.ppr;
-            pa.padb = pp.padb;
-            pa.ringpad = pp.ringpad;
-            pa.live = live;
-            TimedLaunch tl(st, 2.0 * layer_flop_per_clip * (double)n);
-            const dim3 gd(grid), bd(256 * pp.ns * pp.ks);
-            if (pp.ks == 2) {
-              if (!launch_pairk_vf(dA, dil_of(d, i + 1), gd, bd, st, pa))
-                return fail(HONK_ERR_UNSUPPORTED, "block16k: no instance for dilations %d, %d", dA, dil_of(d, i + 1));
-            } else if (FM == 0 && pp.ns == 2 && pp.padb > 0) {
-              if (!launch_pair2i_vf(dA, dil_of(d, i + 1), gd, bd, st, pa))
-                return fail(HONK_ERR_UNSUPPORTED, "block16p: no two-stream tap-step instance for dilations %d, %d", dA,
-                            dil_of(d, i + 1));
-            } else if (FM == 0 && pp.ns == 2) launch_pair2t_vf(pp.ppr, pp.lin, gd, bd, st, pa);
-            else if (!launch_pair_vf(FM, pp.ppr, pp.ppr == 4 && pp.padb > 0, dA, dil_of(d, i + 1), gd, bd, st, pa))
-              return fail(HONK_ERR_UNSUPPORTED, "block16p: no tap-step instance for dilations %d, %d", dA,
-                          dil_of(d, i + 1));
-            HONK_LAUNCH_CHECK("res block16p_kernel");
-            tl.done(st);
-            ++i;  // layer i + 1 done too
-            continue;
-          }
-          const PairPlan lp = last_at(L, d, FM, i);
-          if (lp.ok) {
-            Block16PArgs pa;
-            pa.R = R;  // the last (odd) layer reads R
-            pa.wA = pa.wB = (const char*)(frb + (size_t)(i - 1) * frl);
-            pa.chunk_bytes = (unsigned)((size_t)n * L.H * L.W * L.CP * 2 * SP);
-            pa.nclips = (int)n;
-            pa.H = L.H;
-            pa.W = L.W;
-            pa.d = dil_of(d, i);
-            pa.lgd = 0;
-            while ((1 << pa.lgd) < pa.d) ++pa.lgd;
-            pa.sB = 1;
-            pa.lag = 0;
-            pa.NRA = lp.NRA;
-            pa.NRB = lp.NRB;
-            pa.slotb = lp.slotb;
-            pa.ppr = lp.ppr;
-            pa.padb = lp.padb;
-            pa.ringpad = lp.ringpad;
-            pa.live = live;
-            pa.chsum = chsum;
-            TimedLaunch tl(st, layer_flop_per_clip * (double)n);
-            const dim3 gd(grid), bd(128 * lp.ns);
-            launch_last_vf(FM, pa.d, gd, bd, st, pa);
-            HONK_LAUNCH_CHECK("res block16l_kernel");
-            tl.done(st);
-            parts_last = 2;
-            continue;
-          }
-        }
-        Block16WArgs a;
-        a.in = even ? X : R;
-        a.res = even ? R : nullptr;
-        a.out = (i == L.L) ? nullptr : (even ? R : X);
-        a.wfrag = (const char*)(frb + (size_t)(i - 1) * frl);
-        a.chsum = (i == L.L) ? chsum : nullptr;
-        a.H = L.H;
-        a.W = L.W;
-        a.dil = dil_of(d, i);
-        a.TH = plan_w_th(L, FM, a.dil);
-        const BandGeo bg = band_geo(L.H, a.dil, a.TH);
-        a.nbc = bg.nbc;
-        a.rem = bg.rem;
-        a.nb1 = bg.nb1;
-        a.nb0 = bg.nb0;
-        a.lgd = 0;
-        while ((1 << a.lgd) < a.dil) ++a.lgd;
-        if ((int64_t)n * a.nbc > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
-        a.ntiles = (int)(n * a.nbc);
-        a.live = live;
-        if (i == L.L) parts_last = a.nbc * 4;
-        TimedLaunch tl(st, layer_flop_per_clip * (double)n);
-        rc = dispatch_block16w(L.NT, FM, a, st);
-        tl.done(st);
-        if (rc) return rc;
-      }
-      const float* bn_last = packed + L.off_bn + (size_t)2 * L.CP * (L.L - 1);
-      if (last_stored) {
-        // the last layer was a pair's B layer (bf16): it stored its output in R
-        if (L.CP != 48 || SP != 1) return fail(HONK_ERR_UNSUPPORTED, "tail_act_kernel: 48 bf16 channels only");
-        hipLaunchKernelGGL(tail_act_kernel, dim3((unsigned)n), dim3(256), 0, st, R, packed + L.off_wout,
-                           packed + L.off_bout, logits + c0 * L.NL, L.H * L.W, L.C, L.NL, bn_last, bn_last + L.CP);
-        HONK_LAUNCH_CHECK("res tail_act_kernel");
-        continue;
-      }
-      if (live.count) {
-        hipLaunchKernelGGL(tail_sum_live_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
-                           packed + L.off_bout, logits + c0 * L.NL, parts_last, L.H * L.W, L.C, L.CP, L.NL, bn_last,
-                           bn_last + L.CP, live);
-        HONK_LAUNCH_CHECK("res tail_sum_live_kernel (weight-stationary)");
-        continue;
-      }
-      hipLaunchKernelGGL(tail_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
-                         packed + L.off_bout, logits + c0 * L.NL, parts_last, L.H * L.W, L.C, L.CP, L.NL,
-                         bn_last, bn_last + L.CP, tail_cs, packed + L.off_range + HONK_NUM_OUT_SCALE,
-                         flags ? flags + c0 : nullptr, (float)HONK_F16X2_Z_MAX);
-      HONK_LAUNCH_CHECK("res tail_sum_kernel (weight-stationary)");
     }
-    return HONK_OK;
+    rc = run_tail16(c, *sch, logits + c0 * L.NL, tail_cs, flags ? flags + c0 : nullptr);
+    if (rc) return rc;
   }
-  {
-    // row-band kernel: tiles = (clip, dilation class, band of TH class rows)
-    int nbc_last = 0;
-    for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
-      const int64_t n = (batch - c0 < chunk) ? batch - c0 : chunk;
-      rc = (SP == 2) ? launch_conv0_16<1, false>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st, nullptr,
-                                                 live)
-                     : launch_conv0_16<0, false>(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st);
-      if (rc) return rc;
-      for (int i = 1; i <= L.L; ++i) {
-        const bool even = (i % 2) == 0;
-        Block16RArgs a;
-        a.in = even ? X : R;
-        a.res = even ? R : nullptr;
-        a.out = (i == L.L) ? nullptr : (even ? R : X);
-        a.bfrag = (const uint4*)(SP == 2 ? packed + L.off_fragx3 + (size_t)(i - 1) * L.fragx3_floats
-                                         : packed + L.off_frag16 + (size_t)(i - 1) * L.frag16_floats);
-        a.bias = packed + L.off_bias16 + (size_t)16 * L.CP * (i - 1);
-        a.chsum = (i == L.L) ? chsum : nullptr;
-        a.H = L.H;
-        a.W = L.W;
-        a.dil = d->use_dilation ? (1 << ((i - 1) / 3)) : 1;
-        a.TH = pr.TH;
-        const BandGeo bg = band_geo(L.H, a.dil, pr.TH);
-        a.nbc = bg.nbc;
-        a.rem = bg.rem;
-        a.nb1 = bg.nb1;
-        a.nb0 = bg.nb0;
-        if ((int64_t)n * a.nbc > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
-        a.ntiles = (int)(n * a.nbc);
-        a.live = live;
-        if (i == L.L) nbc_last = a.nbc;
-        TimedLaunch tl(st, layer_flop_per_clip * (double)n);
-        rc = dispatch_block16r(pr, SP, a, st);
-        tl.done(st);
-        if (rc) return rc;
-      }
-      const float* bn_last = packed + L.off_bn + (size_t)2 * L.CP * (L.L - 1);
-      if (live.count) {
-        hipLaunchKernelGGL(tail_sum_live_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
-                           packed + L.off_bout, logits + c0 * L.NL, nbc_last * 8 * pr.MT, L.H * L.W, L.C, L.CP, L.NL,
-                           bn_last, bn_last + L.CP, live);
-        HONK_LAUNCH_CHECK("res tail_sum_live_kernel (bf16 row-band)");
-        continue;
-      }
-      hipLaunchKernelGGL(tail_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
-                         packed + L.off_bout, logits + c0 * L.NL, nbc_last * 8 * pr.MT, L.H * L.W, L.C, L.CP, L.NL,
-                         bn_last, bn_last + L.CP, tail_cs, packed + L.off_range + HONK_NUM_OUT_SCALE, (int*)nullptr, 0.f);
-      HONK_LAUNCH_CHECK("res tail_sum_kernel (bf16 row-band)");
-    }
-    return HONK_OK;
-  }
+  return HONK_OK;
 }
 
 #endif  // HONK_RES_VF_TU
@@ -2208,50 +2209,26 @@ int honk_res_launch_plan(const honk_res_desc* d, int64_t batch, int32_t n_cus, i
   int rc = make_layout(d, &L);
   if (rc) return rc;
   if (batch < 1) return fail(HONK_ERR_ARG, "batch < 1");
-  const int64_t n = chunk_clips(L, batch);
+  const Switches sw = read_switches();
+  const int64_t n = chunk_clips(L, sw, batch);
   int grid = n_cus > 0 ? n_cus : cu_count();
   if (grid > n) grid = (int)n;
-  int cnt = 0;
-  auto put = [&](int k) {
-    if (kinds && cnt < max_kinds) kinds[cnt] = k;
-    ++cnt;
-  };
-  if (L.prec == HONK_PREC_F32) {
-    for (int i = 1; i <= L.L; ++i) put(HONK_KERNEL_BLOCK_F32);
-    return cnt;
-  }
-  const int FM = fmt_of(L.prec), SP = sp_of(FM);
-  if (plan_block16r(L, SP).TH == 0) return fail(HONK_ERR_UNSUPPORTED, "width beyond the row-band staging plan");
-  if (use_n_kernel(L, d, FM)) {
-    put(HONK_KERNEL_NET);
-    return cnt;
-  }
-  if (!use_w_kernel(L, d, FM)) {
-    if (FM == 2) return fail(HONK_ERR_UNSUPPORTED, "f16x2: outside the weight-stationary / pair kernels' envelope");
-    for (int i = 1; i <= L.L; ++i) put(HONK_KERNEL_ROWBAND);
-    return cnt;
-  }
-  for (int i = 1; i <= L.L; ++i) {
-    const PairPlan pp = pair_at(L, d, FM, n, grid, i);
-    if (pp.ok) {
-      put(pp.ks == 2 ? HONK_KERNEL_PAIR_KS : HONK_KERNEL_PAIR);
-      ++i;
-    } else if (last_at(L, d, FM, i).ok) {
-      put(HONK_KERNEL_LAST);
-    } else {
-      put(HONK_KERNEL_WSTAT);
-    }
-  }
+  const Schedule s = plan_chunk(L, d, sw, plan_path(L, d, sw), n, grid);
+  if (s.path == PATH_NO_WIDTH) return fail(HONK_ERR_UNSUPPORTED, "width beyond the row-band staging plan");
+  if (s.path == PATH_NO_F16X2)
+    return fail(HONK_ERR_UNSUPPORTED, "f16x2: outside the weight-stationary / pair kernels' envelope");
+  const int cnt = (int)s.steps.size();
+  for (int k = 0; kinds && k < cnt && k < max_kinds; ++k) kinds[k] = s.steps[k].kind;
   return cnt;
 }
 
 }  // extern "C"
 
 // honk_res_workspace_bytes without the f16x2 admission's regions (below)
-static size_t ws_bytes_plain(const honk_res_desc* d, int64_t batch) {
+static size_t ws_bytes_plain(const honk_res_desc* d, const Switches& sw, int64_t batch) {
   Layout L;
   if (make_layout(d, &L) != HONK_OK || batch < 1) return 0;
-  const int64_t ch = chunk_clips(L, batch);
+  const int64_t ch = chunk_clips(L, sw, batch);
   if (L.prec != HONK_PREC_F32) {
     const int FM = fmt_of(L.prec), SP = sp_of(FM);
     if (L.L < 1) {
@@ -2263,21 +2240,15 @@ static size_t ws_bytes_plain(const honk_res_desc* d, int64_t batch) {
            "use precision f32)", L.ph, L.pw);
       return 0;
     }
+    const Path path = plan_path(L, d, sw);
+    if (path != PATH_WSTAT && path != PATH_ROWBAND) {
+      refuse_path(L, path);
+      return 0;
+    }
     const PlanR pr = plan_block16r(L, SP);
-    if (pr.TH == 0) {
-      fail(HONK_ERR_UNSUPPORTED, "bf16/bf16x3: feature-map width %d exceeds the row-band staging plan "
-           "(use precision f32)", L.W);
-      return 0;
-    }
-    const bool wpath = L.L > 0 && use_w_kernel(L, d, FM);
-    if (FM == 2 && !wpath) {
-      fail(HONK_ERR_UNSUPPORTED, "f16x2 runs on the weight-stationary / pair kernels only: %d maps, %dx%d (pooled) "
-           "map, pool %dx%d is outside their envelope (use precision f32 or bf16x3)", L.C, L.H, L.W, L.ph, L.pw);
-      return 0;
-    }
     const int nb = max_bands_per_clip(L, pr.TH, d->use_dilation);
     size_t parts = (size_t)nb * 8 * pr.MT;  // row-band kernel: [tile][wave][m-tile] channel sums
-    if (wpath) {
+    if (path == PATH_WSTAT) {
       const size_t pw = (size_t)bands_w(L, d, FM, L.L) * 4;  // weight-stationary: [tile][wave]
       if (pw > parts) parts = pw;
     }
@@ -2297,25 +2268,21 @@ struct F16Check {
   int64_t rc;
   size_t main, flags, list, count, gx, glog, total;
 };
-static bool f16x2_rerun_on() {
-  const char* e = getenv("HONK_F16X2_RERUN");
-  return !(e && e[0] == '0');
-}
 static honk_res_desc rerun_desc(const honk_res_desc* d) {
   honk_res_desc e = *d;
   e.precision = HONK_PREC_BF16X3;
   return e;
 }
-static bool f16_check_plan(const honk_res_desc* d, int64_t batch, F16Check* p) {
+static bool f16_check_plan(const honk_res_desc* d, const Switches& sw, int64_t batch, F16Check* p) {
   Layout L;
   if (make_layout(d, &L) != HONK_OK || batch < 1) return false;
-  const size_t f16 = ws_bytes_plain(d, batch);
+  const size_t f16 = ws_bytes_plain(d, sw, batch);
   const honk_res_desc e = rerun_desc(d);
   if (f16 == 0) return false;
-  int64_t rc = chunk_clips(L, batch) / 2;
+  int64_t rc = chunk_clips(L, sw, batch) / 2;
   if (rc < 1) rc = 1;
-  while (rc > 1 && ws_bytes_plain(&e, rc) > f16) rc /= 2;
-  const size_t r = ws_bytes_plain(&e, rc);
+  while (rc > 1 && ws_bytes_plain(&e, sw, rc) > f16) rc /= 2;
+  const size_t r = ws_bytes_plain(&e, sw, rc);
   if (r == 0) {
     fail(HONK_ERR_UNSUPPORTED, "f16x2 admission: the bf16x3 re-run does not take this shape");
     return false;
@@ -2332,17 +2299,19 @@ static bool f16_check_plan(const honk_res_desc* d, int64_t batch, F16Check* p) {
   return true;
 }
 
+static size_t ws_need(const honk_res_desc* d, const Switches& sw, int64_t batch) {
+  if (d && d->precision == HONK_PREC_F16X2 && sw.rerun_on()) {
+    F16Check p;
+    return f16_check_plan(d, sw, batch, &p) ? p.total : 0;
+  }
+  return ws_bytes_plain(d, sw, batch);
+}
+
 static thread_local int64_t g_rerun = 0;
 
 extern "C" {
 
-size_t honk_res_workspace_bytes(const honk_res_desc* d, int64_t batch) {
-  if (d && d->precision == HONK_PREC_F16X2 && f16x2_rerun_on()) {
-    F16Check p;
-    return f16_check_plan(d, batch, &p) ? p.total : 0;
-  }
-  return ws_bytes_plain(d, batch);
-}
+size_t honk_res_workspace_bytes(const honk_res_desc* d, int64_t batch) { return ws_need(d, read_switches(), batch); }
 
 int64_t honk_res_rerun_count(void) { return g_rerun; }
 
@@ -2435,11 +2404,11 @@ int honk_res_numerics(const honk_res_desc* d, const float* packed, float* rec, i
 // (8.4e-5 .. 1.6e-3); bf16x3 carries ~2^5 more significant bits per activation.
 #define HONK_F16X2_RHO_MAX 3.5f
 #define HONK_BF16X3_RHO_MAX 100.f
-static bool prec_supported(const honk_res_desc* d, int p) {
+static bool prec_supported(const honk_res_desc* d, const Switches& sw, int p) {
   honk_res_desc e = *d;
   e.precision = p;
   const std::string keep = get_error();
-  const bool ok = honk_res_workspace_bytes(&e, 1) != 0 && honk_res_packed_floats(&e) != 0;
+  const bool ok = ws_need(&e, sw, 1) != 0 && honk_res_packed_floats(&e) != 0;
   set_error("%s", keep.c_str());
   return ok;
 }
@@ -2450,6 +2419,7 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
   e.precision = HONK_PREC_F32;
   int rc = make_layout(&e, &L);
   if (rc) return rc;
+  const Switches sw = read_switches();
   char buf[256];
   buf[0] = 0;
   auto done = [&](int p) {
@@ -2458,7 +2428,7 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
   };
   if (requested == HONK_PREC_F32) return done(HONK_PREC_F32);
   if (requested == HONK_PREC_BF16) {
-    if (prec_supported(d, HONK_PREC_BF16)) return done(HONK_PREC_BF16);
+    if (prec_supported(d, sw, HONK_PREC_BF16)) return done(HONK_PREC_BF16);
     snprintf(buf, sizeof buf, "bf16 does not take this shape (%s)", get_error());
     return done(HONK_PREC_F32);
   }
@@ -2468,7 +2438,7 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
   const float rho = rec[HONK_NUM_RHO];
   if (requested != HONK_PREC_BF16X3) {
     const char* why = nullptr;
-    if (!prec_supported(d, HONK_PREC_F16X2)) why = "outside the f16x2 kernels' envelope";
+    if (!prec_supported(d, sw, HONK_PREC_F16X2)) why = "outside the f16x2 kernels' envelope";
     else if (L.ph * L.pw > 1 || L.H * L.W < 4040 || L.C < 32)
       why = "the 1e-4 contract of f16x2 covers unpooled maps of >= 4040 pixels and >= 32 feature maps (res15)";
     else if (rec[HONK_NUM_F16_OVERFLOW] != 0.f) why = "a folded weight is beyond fp16's range";
@@ -2477,14 +2447,45 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
     snprintf(buf, sizeof buf, "f16x2 not taken: %s (rho %.3g, bound %.3g)", why, (double)rho,
              (double)HONK_F16X2_RHO_MAX);
   }
-  if (prec_supported(d, HONK_PREC_BF16X3) && rho <= HONK_BF16X3_RHO_MAX) return done(HONK_PREC_BF16X3);
+  if (prec_supported(d, sw, HONK_PREC_BF16X3) && rho <= HONK_BF16X3_RHO_MAX) return done(HONK_PREC_BF16X3);
   const size_t k = strlen(buf);
   snprintf(buf + k, sizeof buf - k, "%sbf16x3 not taken (rho %.3g, bound %.3g, %s)", k ? "; " : "", (double)rho,
-           (double)HONK_BF16X3_RHO_MAX, prec_supported(d, HONK_PREC_BF16X3) ? "supported" : "unsupported shape");
+           (double)HONK_BF16X3_RHO_MAX, prec_supported(d, sw, HONK_PREC_BF16X3) ? "supported" : "unsupported shape");
   return done(HONK_PREC_F32);
 }
 
 }  // extern "C"
+
+// The f16x2 admission's re-run: the first `bound` flagged clips in bf16x3, p.rc per round --
+// gather, forward, scatter.  live.count == nullptr: bound is the count the host has read.
+// Else (the ordered entry) bound = live.cap, and the round at offset o runs clamp(min(count,
+// cap) - o, 0, n) clips (live_clips), its other workgroups return at once; flagged clips past
+// cap keep their f16x2 logits.
+static int rerun_flagged(const Layout& L, const honk_res_desc* d, const Switches& sw, const F16Check& p,
+                         const float* packed, const float* x, float* logits, void* workspace, int64_t bound,
+                         LiveRef live, hipStream_t st) {
+  const honk_res_desc e = rerun_desc(d);
+  Layout L3;
+  int rc = make_layout(&e, &L3);
+  if (rc) return rc;
+  char* ws = (char*)workspace;
+  const int* list = (const int*)(ws + p.list);
+  float* gx = (float*)(ws + p.gx);
+  float* glog = (float*)(ws + p.glog);
+  Schedule sch{};
+  for (int64_t o = 0; o < bound; o += p.rc) {
+    const int64_t n = bound - o < p.rc ? bound - o : p.rc;
+    const LiveRef lv{live.count, live.cap, live.count ? (int)o : 0};
+    hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)n), dim3(256), 0, st, x, list + o, L.Hin * L.Win, gx, lv);
+    HONK_LAUNCH_CHECK("res gather_clips_kernel");
+    rc = forward_bf16(L3, &e, sw, &sch, packed, gx, glog, n, chunk_clips(L3, sw, n), workspace, st, nullptr, lv);
+    if (rc) return rc;
+    hipLaunchKernelGGL(scatter_logits_kernel, dim3((unsigned)cdiv(n * L.NL, 64)), dim3(64), 0, st, glog, list + o,
+                       (int)n, L.NL, logits, lv);
+    HONK_LAUNCH_CHECK("res scatter_logits_kernel");
+  }
+  return HONK_OK;
+}
 
 // honk_res_forward (ordered = false) and honk_res_forward_ordered (true: no host read of
 // the flagged-clip count -- cap and flagged_out are its arguments)
@@ -2505,89 +2506,53 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
     return HONK_OK;
   }
   if (!packed || !x || !logits || !workspace) return fail(HONK_ERR_ARG, "null pointer argument");
-  const size_t need = honk_res_workspace_bytes(d, batch);
+  const Switches sw = read_switches();
+  const size_t need = ws_need(d, sw, batch);
   // (the ordered entry enqueues nothing for a shape the kernels do not take: the reason is set)
   if (ordered && need == 0) return HONK_ERR_UNSUPPORTED;
   if (ws_bytes < need)
     return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t chunk = chunk_clips(L, batch);
+  const int64_t chunk = chunk_clips(L, sw, batch);
+  const bool admission = L.prec == HONK_PREC_F16X2 && sw.rerun_on();
   g_rerun = 0;
-  if (ordered && flagged_out && !(L.prec == HONK_PREC_F16X2 && f16x2_rerun_on())) {
+  if (ordered && flagged_out && !admission) {
     hipLaunchKernelGGL(count_out_kernel, dim3(1), dim3(1), 0, st, (const int*)nullptr, flagged_out);
     HONK_LAUNCH_CHECK("res count_out_kernel");
   }
-  if (L.prec == HONK_PREC_F16X2 && f16x2_rerun_on()) {
+  Schedule sch{};
+  if (admission) {
     if (batch > 0x7fffffff) return fail(HONK_ERR_ARG, "f16x2: batch beyond 2^31 clips");
     F16Check p;
-    if (!f16_check_plan(d, batch, &p)) return fail(HONK_ERR_UNSUPPORTED, "%s", get_error());
+    if (!f16_check_plan(d, sw, batch, &p)) return fail(HONK_ERR_UNSUPPORTED, "%s", get_error());
     char* ws = (char*)workspace;
     int* flags = (int*)(ws + p.flags);
-    int* list = (int*)(ws + p.list);
     int* count = (int*)(ws + p.count);
-    rc = forward_bf16(L, d, packed, x, logits, batch, chunk, workspace, st, flags);
+    rc = forward_bf16(L, d, sw, &sch, packed, x, logits, batch, chunk, workspace, st, flags);
     if (rc) return rc;
-    hipLaunchKernelGGL(flag_compact_kernel, dim3(1), dim3(1024), 0, st, flags, batch, list, count);
+    hipLaunchKernelGGL(flag_compact_kernel, dim3(1), dim3(1024), 0, st, flags, batch, (int*)(ws + p.list), count);
     HONK_LAUNCH_CHECK("res flag_compact_kernel");
     if (ordered) {
-      // every round the capacity allows, each on the clips the device's count leaves it: the
-      // round at offset o runs clamp(min(count, cap) - o, 0, n) clips (live_clips), its
-      // other workgroups return at once; flagged clips past cap keep their f16x2 logits
       if (flagged_out) {
         hipLaunchKernelGGL(count_out_kernel, dim3(1), dim3(1), 0, st, (const int*)count, flagged_out);
         HONK_LAUNCH_CHECK("res count_out_kernel");
       }
       if (cap <= 0 || cap > batch) cap = batch;
-      const honk_res_desc e = rerun_desc(d);
-      Layout L3;
-      rc = make_layout(&e, &L3);
-      if (rc) return rc;
-      float* gx = (float*)(ws + p.gx);
-      float* glog = (float*)(ws + p.glog);
-      for (int64_t o = 0; o < cap; o += p.rc) {
-        const int64_t n = cap - o < p.rc ? cap - o : p.rc;
-        const LiveRef live{count, (int)cap, (int)o};
-        hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)n), dim3(256), 0, st, x, list + o, L.Hin * L.Win, gx,
-                           live);
-        HONK_LAUNCH_CHECK("res gather_clips_kernel");
-        rc = forward_bf16(L3, &e, packed, gx, glog, n, chunk_clips(L3, n), workspace, st, nullptr, live);
-        if (rc) return rc;
-        hipLaunchKernelGGL(scatter_logits_kernel, dim3((unsigned)cdiv(n * L.NL, 64)), dim3(64), 0, st, glog,
-                           list + o, (int)n, L.NL, logits, live);
-        HONK_LAUNCH_CHECK("res scatter_logits_kernel");
-      }
-      return HONK_OK;
+      return rerun_flagged(L, d, sw, p, packed, x, logits, workspace, cap, LiveRef{count, (int)cap, 0}, st);
     }
     int flagged = 0;
     HONK_HIP_CHECK(hipMemcpyAsync(&flagged, count, sizeof(int), hipMemcpyDeviceToHost, st));
     HONK_HIP_CHECK(hipStreamSynchronize(st));
     g_rerun = flagged;
-    if (flagged == 0) return HONK_OK;
-    const honk_res_desc e = rerun_desc(d);
-    Layout L3;
-    rc = make_layout(&e, &L3);
-    if (rc) return rc;
-    float* gx = (float*)(ws + p.gx);
-    float* glog = (float*)(ws + p.glog);
-    for (int64_t o = 0; o < flagged; o += p.rc) {
-      const int64_t n = flagged - o < p.rc ? flagged - o : p.rc;
-      hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)n), dim3(256), 0, st, x, list + o, L.Hin * L.Win, gx,
-                         LiveRef{nullptr, 0, 0});
-      HONK_LAUNCH_CHECK("res gather_clips_kernel");
-      rc = forward_bf16(L3, &e, packed, gx, glog, n, chunk_clips(L3, n), workspace, st);
-      if (rc) return rc;
-      hipLaunchKernelGGL(scatter_logits_kernel, dim3((unsigned)cdiv(n * L.NL, 64)), dim3(64), 0, st, glog, list + o,
-                         (int)n, L.NL, logits, LiveRef{nullptr, 0, 0});
-      HONK_LAUNCH_CHECK("res scatter_logits_kernel");
-    }
-    return HONK_OK;
+    return rerun_flagged(L, d, sw, p, packed, x, logits, workspace, flagged, LiveRef{nullptr, 0, 0}, st);
   }
-  if (L.prec != HONK_PREC_F32) return forward_bf16(L, d, packed, x, logits, batch, chunk, workspace, st);
+  if (L.prec != HONK_PREC_F32) return forward_bf16(L, d, sw, &sch, packed, x, logits, batch, chunk, workspace, st);
   const size_t act = (size_t)chunk * L.H * L.W * L.CP;
   float* R = (float*)workspace;
   float* X[2] = {R + act, R + 2 * act};
   float* chsum = R + 3 * act;  // [chunk][nbands][MW][CP] fused-mean partial sums
-  const Plan p = plan_block(L);
+  sch = plan_chunk(L, d, sw, PATH_F32, chunk, cu_count());  // (fp32: one plan whatever the chunk's clips)
+  const Plan p = sch.p32;
   const double layer_flop_per_clip = 2.0 * L.H * L.W * L.C * L.C * 9;
 
   for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
@@ -2595,7 +2560,8 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
     if ((int64_t)n * p.nbands > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
     rc = launch_conv0(L, x + c0 * L.Hin * L.Win, R, packed + L.off_conv0, n, st);
     if (rc) return rc;
-    for (int i = 1; i <= L.L; ++i) {
+    for (const Step& s : sch.steps) {
+      const int i = s.layer;
       BlockArgs a;
       a.in = (i == 1) ? R : X[i & 1];
       const bool even = (i % 2) == 0;
@@ -2607,8 +2573,8 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
       a.bn_shift = a.bn_scale + L.CP;
       a.H = L.H;
       a.W = L.W;
-      a.dil = d->use_dilation ? (1 << ((i - 1) / 3)) : 1;
-      a.TH = p.TH;
+      a.dil = dil_of(d, i);
+      a.TH = s.TH;
       a.nbands = p.nbands;
       a.ntiles = (int)(n * p.nbands);
       a.chsum = (i == L.L) ? chsum : nullptr;  // last layer: fused spatial mean, no stores
@@ -2625,7 +2591,7 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
       HONK_LAUNCH_CHECK("res tail_kernel");
     } else {
       hipLaunchKernelGGL(tail_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, chsum, packed + L.off_wout,
-                         packed + L.off_bout, logits + c0 * L.NL, p.nbands * MW, L.H * L.W, L.C, L.CP, L.NL,
+                         packed + L.off_bout, logits + c0 * L.NL, sch.parts_last, L.H * L.W, L.C, L.CP, L.NL,
                          (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                          (const float*)nullptr, (int*)nullptr, 0.f);
       HONK_LAUNCH_CHECK("res tail_sum_kernel");
@@ -2648,9 +2614,10 @@ int honk_res_forward_ordered(const honk_res_desc* d, const float* packed, const 
 }
 
 int64_t honk_res_rerun_clips(const honk_res_desc* d, int64_t batch) {
-  if (!d || d->precision != HONK_PREC_F16X2 || !f16x2_rerun_on()) return 0;
+  const Switches sw = read_switches();
+  if (!d || d->precision != HONK_PREC_F16X2 || !sw.rerun_on()) return 0;
   F16Check p;
-  return f16_check_plan(d, batch, &p) ? p.rc : 0;
+  return f16_check_plan(d, sw, batch, &p) ? p.rc : 0;
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@
 //
 // This file includes res.hip with HONK_RES_VF_TU defined: the device templates and
 // their argument structs only (no host code, no non-template kernels), and defines
-// the two launchers res.hip's forward_bf16 calls.
+// the launchers res.hip's run_pair calls.
 //
 // Scheduling choices measured under this unit's flag are set here too.  HONK_PAIR_DTOP (see
 // res_bf16p.inc, run_mtile): the A waves' k-steps 0 and 1 of a step form one scheduling
@@ -27,8 +27,8 @@
 namespace honk {
 namespace res {
 
-// the pair (layers i, i + 1; dilations dA, dB) -- res.hip:forward_bf16, which has
-// planned it (PairPlan pp: ppr, padb, ns).  FM 2 with pad columns: the tap-step
+// the pair (layers i, i + 1; dilations dA, dB) -- res.hip:run_pair, from the step
+// plan_chunk planned (PairPlan pp: ppr, padb, ns).  FM 2 with pad columns: the tap-step
 // instances (pair_imm).  Returns false when no instance matches (the caller reports
 // HONK_ERR_UNSUPPORTED); the two-stream bf16 instance (ns == 2) is not here.
 bool launch_pair_vf(int FM, int ppr, bool imm, int dA, int dB, dim3 gd, dim3 bd, hipStream_t st,
@@ -74,18 +74,6 @@ bool launch_pair2i_vf(int dA, int dB, dim3 gd, dim3 bd, hipStream_t st, const Bl
   }
   HONK_P2I(1, 1) HONK_P2I(1, 2) HONK_P2I(2, 2) HONK_P2I(4, 4) HONK_P2I(8, 8)
 #undef HONK_P2I
-  return false;
-}
-
-// f16x2 with the contraction split over two waves per SIMD (res_bf16k.inc)
-bool launch_pairk_vf(int dA, int dB, dim3 gd, dim3 bd, hipStream_t st, const Block16PArgs& pa) {
-#define HONK_PK(a_, b_)                                                       \
-  if (dA == a_ && dB == b_) {                                                 \
-    hipLaunchKernelGGL((block16k_kernel<a_, b_>), gd, bd, 0, st, pa);        \
-    return true;                                                              \
-  }
-  HONK_PK(1, 1) HONK_PK(1, 2) HONK_PK(2, 2) HONK_PK(4, 4) HONK_PK(4, 8) HONK_PK(8, 8)
-#undef HONK_PK
   return false;
 }
 

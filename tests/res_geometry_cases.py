@@ -32,11 +32,11 @@ from golden_util import ref_configs
 PRECS = ("bf16x3", "f16x2", "bf16")
 KERNEL_OF = {"F": "block_kernel", "R": "block16r_kernel", "W": "block16w_kernel", "P": "block16p_kernel",
              "L": "block16l_kernel"}
-# "forced-p": pairs wherever they plan, the last layer on the weight-stationary kernel, no
-# K-split variant -- the environment of the pair-vs-w bitwise identity
-FORCED_P = dict(HONK_RES_KERNEL="p", HONK_LAST_KERNEL="w", HONK_PAIR_KS="0")
+# "forced-p": pairs wherever they plan, the last layer on the weight-stationary kernel --
+# the environment of the pair-vs-w bitwise identity
+FORCED_P = dict(HONK_RES_KERNEL="p", HONK_LAST_KERNEL="w")
 # every variable that changes the res forward's dispatch: cleared before each run
-ENV_VARS = ("HONK_RES_KERNEL", "HONK_LAST_KERNEL", "HONK_PAIR_KS", "HONK_PAIR_STREAMS", "HONK_PAIR_IMM2",
+ENV_VARS = ("HONK_RES_KERNEL", "HONK_LAST_KERNEL", "HONK_PAIR_STREAMS", "HONK_PAIR_IMM2",
             "HONK_PAIR_LIN", "HONK_F16X2_RERUN", "HONK_RES_CHUNK", "HONK_CONV0")
 BMAX = 600
 BF16_BOUND = 8e-3           # test_gpu_bf16.BF16_BOUND (relative past |logit| = 1)

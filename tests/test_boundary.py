@@ -292,14 +292,10 @@ def test_res_launch_plan_host_only(monkeypatch):
     assert plan("res15", "bf16x3") == ["block16w_kernel"] * 13
     monkeypatch.setenv("HONK_RES_KERNEL", "r")
     assert plan("res15", "bf16x3") == ["block16r_kernel"] * 13
-    monkeypatch.setenv("HONK_RES_KERNEL", "n")  # the whole-stack kernel (opt-in)
-    assert plan("res8", "bf16") == ["block16n_kernel"]
-    assert plan("res8-narrow", "bf16") == ["block16n_kernel"]
-    monkeypatch.setenv("HONK_RES_KERNEL", "r")
     assert plan("res8", "bf16") == ["block16r_kernel"] * 6
-    monkeypatch.setenv("HONK_RES_KERNEL", "n")
-    assert plan("res26-narrow", "bf16") == ["block16r_kernel"] * 24  # 50 x 20 maps: no room for three images
-    assert plan("res15", "bf16") == ["block16p_kernel"] * 6 + ["block16l_kernel"]  # dilated: not taken
+    monkeypatch.setenv("HONK_RES_KERNEL", "n")  # (the removed whole-stack kernel's) an unknown value: ignored
+    assert plan("res26-narrow", "bf16") == ["block16r_kernel"] * 24
+    assert plan("res15", "bf16") == ["block16p_kernel"] * 6 + ["block16l_kernel"]
 
 
 def test_res_launch_plan_errors_raise_with_reason():

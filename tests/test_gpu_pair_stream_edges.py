@@ -74,7 +74,6 @@ def _pair_vs_w(monkeypatch, m, x):
     B = len(x)
     monkeypatch.setenv("HONK_RES_KERNEL", "p")
     monkeypatch.setenv("HONK_LAST_KERNEL", "w")
-    monkeypatch.setenv("HONK_PAIR_KS", "0")
     plan = _native.res_launch_plan(m._desc(101, 40), B)
     assert "block16p_kernel" in plan and "block16l_kernel" not in plan, plan
     outp = _run(m, x)
