@@ -97,6 +97,7 @@ _PROTOS = {
     "honk_conv3x3_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64] + [ctypes.c_int32] * 5
                          + [ctypes.c_void_p]),
     "honk_conv3x3_check": (ctypes.c_int, [ctypes.c_int32] * 4),
+    "honk_conv3x3_plan": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)]),
     "honk_conv3x3_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64] + [ctypes.c_int32] * 4),
     "honk_conv3x3_wgrad_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64] + [ctypes.c_int32] * 4
                                + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
@@ -275,3 +276,25 @@ def res_select_precision(desc, rec, requested: str):
     if p < 0:
         check(p, "honk_res_select_precision")
     return PRECISION_NAMES[p], note.value.decode(errors="replace")
+
+
+# HONK_CONV3X3_FAMILY_* / HONK_CONV3X3_PLAN_* of include/honk_hip.h
+CONV3X3_FAMILIES = {0: None, 1: "d", 2: "m", 3: "v"}
+CONV3X3_PLAN_COUNT = 16
+
+
+def conv3x3_plan(batch: int, c: int, h: int, w: int, dil: int, n_cus: int = 0):
+    """honk_conv3x3_plan: the kernels the training block convs run (batch, C, H, W, dil) on
+    under the current environment, or None where the dedicated kernels do not take the shape
+    (the same-conv path).  Host-only.  {"conv": dict(family "d" | "m" | "v", np, fixed, th,
+    nband, grid), "wgrad": dict(family, variant "q" | "h" | "d" | None, fixed, th, nband,
+    grid), "stats": bool, "fold": bool}."""
+    out = (ctypes.c_int32 * CONV3X3_PLAN_COUNT)()
+    check(load().honk_conv3x3_plan(int(batch), int(c), int(h), int(w), int(dil), int(n_cus), out), "honk_conv3x3_plan")
+    if not out[0]:
+        return None
+    return {"conv": dict(family=CONV3X3_FAMILIES[out[1]], np=out[2], fixed=bool(out[3]), th=out[4], nband=out[5],
+                         grid=out[6]),
+            "wgrad": dict(family=CONV3X3_FAMILIES[out[8]], variant=chr(out[9]) if out[9] else None,
+                          fixed=bool(out[10]), th=out[11], nband=out[12], grid=out[13]),
+            "stats": bool(out[7]), "fold": bool(out[14])}

@@ -764,9 +764,9 @@ static int td_rows(int C, int H, int W, int d) {
 
 // the compile-time geometry instance (res26-narrow: 20-pixel maps, d = 1, 25-row tiles)
 // applies; HONK_TD_FIXED=0 turns it off (A/B)
-static bool td_fixed(const Conv3Args& a) {
+static bool td_fixed(int W, const ClassBands& g) {
   const char* e = getenv("HONK_TD_FIXED");
-  return !(e && e[0] == '0') && a.W == 20 && a.g.d == 1 && a.g.TH == 25;
+  return !(e && e[0] == '0') && W == 20 && g.d == 1 && g.TH == 25;
 }
 
 // class rows per conv3x3m_kernel tile: C planes of (TH + 2) x (W + 2d) (+ pad) in TM_XL
@@ -1493,9 +1493,9 @@ static int twd_rows(int C, int H, int W, int d) {
 
 // wgrad3x3d_kernel's compile-time geometry instance (res26-narrow: W = 20, d = 1, 17-row
 // bands); HONK_TD_FIXED=0 turns it off (A/B)
-static bool twd_fixed(const WgradArgs& a) {
+static bool twd_fixed(int W, const ClassBands& g) {
   const char* e = getenv("HONK_TD_FIXED");
-  return !(e && e[0] == '0') && a.W == 20 && a.g.d == 1 && a.g.TH == 17;
+  return !(e && e[0] == '0') && W == 20 && g.d == 1 && g.TH == 17;
 }
 
 // class rows per wgrad3x3m_kernel tile: C x planes of (TH + 2) x (W + 2d) in TW_XL,
@@ -2082,9 +2082,87 @@ static int tc_rows(int C, int H, int W, int d, bool conv = false) {
   const int nb = (hc + th - 1) / th;
   return (hc + nb - 1) / nb;
 }
-static int tc_grid(int64_t tiles) {
-  const int64_t g = 2 * (int64_t)cu_count();
+static int tc_grid(int64_t tiles, int n_cus) {
+  const int64_t g = 2 * (int64_t)n_cus;
   return (int)(tiles < g ? tiles : g);
+}
+
+// ---- the plan of the block convs of one shape: which kernel the forward / input-
+// gradient conv and the weight gradient run, its class-band geometry and grid.  Every
+// launch below and honk_conv3x3_plan read it (n_cus: the device's CU count at a launch).
+enum { FAM_NONE = 0, FAM_DMA = 1, FAM_MFMA = 2, FAM_VALU = 3 };  // HONK_CONV3X3_FAMILY_*
+struct ConvPlan {
+  int family, np;  // np: conv3x3_kernel's pixels per thread (VALU only)
+  bool fixed;      // the compile-time geometry instance (td_fixed)
+  ClassBands g;
+  int grid;
+};
+struct WgradPlan {
+  int family, variant;  // variant (DMA only): 'q', 'h' or 'd' (HONK_WGRAD)
+  bool fixed;           // twd_fixed
+  ClassBands g;
+  int grid;
+};
+struct Plan {
+  ConvPlan conv;
+  WgradPlan wg;
+  int stats;  // the statistics epilogue's grid (conv3x3d_kernel MODE 1 / 2), 0: none
+  bool fold;  // the folded BatchNorm: the epilogue and a DMA-staged weight gradient
+};
+// (C, H, W, d) the dedicated kernels take (tc_check's shape rule)
+static bool plan_shape_ok(int c, int h, int w, int d) {
+  return (c == 19 || c == 45) && h >= 1 && w >= 1 && d >= 1 && d <= 64 && tc_rows(c, h, w, d) >= 1 &&
+         tc_rows(c, h, w, d, true) >= 1;
+}
+// The three planners below take a shape plan_shape_ok accepts (every family then has a
+// band of >= 1 row).  HONK_TRAIN_CONV=m / v keeps the 19-map convs off the LDS-DMA / off
+// both MFMA families (tests compare all three bitwise).
+static void plan_env(int c, bool& no_dma, bool& no_mfma) {
+  const char* ke = getenv("HONK_TRAIN_CONV");
+  no_dma = c != 19 || (ke && (ke[0] == 'v' || ke[0] == 'm'));
+  no_mfma = c != 19 || (ke && ke[0] == 'v');
+}
+// forward / input gradient.  19 maps: the LDS-DMA double-buffered MFMA kernel where it
+// applies (d <= 4, W % 4 == 0), else the register-staged one, else (and 45 maps) VALU
+static ConvPlan conv_plan(int64_t batch, int c, int h, int w, int d, int n_cus) {
+  bool no_dma, no_mfma;
+  plan_env(c, no_dma, no_mfma);
+  ConvPlan cv;
+  const int tdr = no_dma ? 0 : td_rows(c, h, w, d), tmr = no_mfma || tdr > 0 ? 0 : tm_rows(c, h, w, d);
+  cv.family = tdr > 0 ? FAM_DMA : tmr > 0 ? FAM_MFMA : FAM_VALU;
+  cv.g = class_bands(h, d, tdr > 0 ? tdr : tmr > 0 ? tmr : tc_rows(c, h, w, d, true));
+  const int64_t tiles = batch * cv.g.nband;
+  cv.grid = cv.family == FAM_DMA ? (int)std::min<int64_t>(tiles, n_cus) : tc_grid(tiles, n_cus);
+  cv.fixed = cv.family == FAM_DMA && td_fixed(w, cv.g);
+  cv.np = 0;
+  if (cv.family == FAM_VALU)  // output pixels per thread: 1..4 (19 maps) / 1..2 (45 maps)
+    cv.np = std::min<int>(std::max<int>((int)cdiv((int64_t)cv.g.TH * w, 256), 1), c == 19 ? 4 : 2);
+  return cv;
+}
+// the weight gradient: the DMA-staged kernels (HONK_WGRAD=d: wgrad3x3d_kernel instead of
+// wgrad3x3q_kernel, =h: the hybrid -- 16x16x4 for outputs 0..15; A/B, tests), the
+// register-staged MFMA one, the VALU one
+static WgradPlan wgrad_plan(int64_t batch, int c, int h, int w, int d, int n_cus) {
+  bool no_dma, no_mfma;
+  plan_env(c, no_dma, no_mfma);
+  WgradPlan wg;
+  const int td = no_dma ? 0 : twd_rows(c, h, w, d), tw = no_mfma || td > 0 ? 0 : tw_rows(c, h, w, d);
+  wg.family = td > 0 ? FAM_DMA : tw > 0 ? FAM_MFMA : FAM_VALU;
+  wg.g = class_bands(h, d, td > 0 ? td : tw > 0 ? tw : tc_rows(c, h, w, d));
+  const int64_t tiles = batch * wg.g.nband;
+  wg.grid = wg.family == FAM_DMA ? (int)std::min<int64_t>(tiles, n_cus) : tc_grid(tiles, n_cus);
+  wg.fixed = wg.family == FAM_DMA && twd_fixed(w, wg.g);
+  const char* we = getenv("HONK_WGRAD");
+  wg.variant = wg.family != FAM_DMA ? 0 : we && we[0] == 'd' ? 'd' : we && we[0] == 'h' ? 'h' : 'q';
+  return wg;
+}
+static Plan plan(int64_t batch, int c, int h, int w, int d, int n_cus) {
+  Plan p;
+  p.conv = conv_plan(batch, c, h, w, d, n_cus);
+  p.wg = wgrad_plan(batch, c, h, w, d, n_cus);
+  p.stats = p.conv.family == FAM_DMA ? p.conv.grid : 0;
+  p.fold = p.stats > 0 && p.wg.family == FAM_DMA;
+  return p;
 }
 
 }  // namespace train
@@ -2112,7 +2190,7 @@ int tc_check(const void* a, const void* b, const void* c, int64_t batch, int32_t
   if (batch < 0 || h < 1 || w < 1) return fail(HONK_ERR_ARG, "bad conv3x3 shape (B=%lld H=%d W=%d)", (long long)batch, h, w);
   if (d < 1 || d > 64) return fail(HONK_ERR_ARG, "conv3x3: dilation %d (1..64)", d);
   if (ch != 19 && ch != 45) return fail(HONK_ERR_UNSUPPORTED, "conv3x3 training kernels: C=%d (19 or 45)", ch);
-  if (train::tc_rows(ch, h, w, d) < 1 || train::tc_rows(ch, h, w, d, true) < 1)
+  if (!train::plan_shape_ok(ch, h, w, d))
     return fail(HONK_ERR_UNSUPPORTED, "conv3x3: width %d at dilation %d too large", w, d);
   if (batch * (int64_t)h > 0x3fffffff) return fail(HONK_ERR_ARG, "conv3x3: batch too large");
   return HONK_OK;
@@ -2124,6 +2202,34 @@ extern "C" int honk_conv3x3_check(int32_t c, int32_t h, int32_t w_, int32_t dil)
   return tc_check(&dummy, &dummy, &dummy, 1, c, h, w_, dil);
 }
 
+extern "C" int honk_conv3x3_plan(int64_t batch, int32_t c, int32_t h, int32_t w_, int32_t dil, int32_t n_cus,
+                                 int32_t* out) {
+  if (!out) return fail(HONK_ERR_ARG, "null pointer argument");
+  if (batch < 1 || n_cus < 0) return fail(HONK_ERR_ARG, "conv3x3 plan: batch %lld, %d CUs", (long long)batch, n_cus);
+  for (int i = 0; i < HONK_CONV3X3_PLAN_COUNT; ++i) out[i] = 0;
+  static const float dummy = 0.f;
+  const int rc = tc_check(&dummy, &dummy, &dummy, batch, c, h, w_, dil);
+  if (rc == HONK_ERR_UNSUPPORTED) return HONK_OK;  // out[HONK_CONV3X3_PLAN_OK] == 0: the same-conv path's shape
+  if (rc) return rc;
+  const train::Plan p = train::plan(batch, c, h, w_, dil, n_cus > 0 ? n_cus : cu_count());
+  out[HONK_CONV3X3_PLAN_OK] = 1;
+  out[HONK_CONV3X3_PLAN_CONV_FAMILY] = p.conv.family;
+  out[HONK_CONV3X3_PLAN_CONV_NP] = p.conv.np;
+  out[HONK_CONV3X3_PLAN_CONV_FIXED] = p.conv.fixed;
+  out[HONK_CONV3X3_PLAN_CONV_TH] = p.conv.g.TH;
+  out[HONK_CONV3X3_PLAN_CONV_NBAND] = p.conv.g.nband;
+  out[HONK_CONV3X3_PLAN_CONV_GRID] = p.conv.grid;
+  out[HONK_CONV3X3_PLAN_STATS] = p.stats > 0;
+  out[HONK_CONV3X3_PLAN_WGRAD_FAMILY] = p.wg.family;
+  out[HONK_CONV3X3_PLAN_WGRAD_VARIANT] = p.wg.variant;
+  out[HONK_CONV3X3_PLAN_WGRAD_FIXED] = p.wg.fixed;
+  out[HONK_CONV3X3_PLAN_WGRAD_TH] = p.wg.g.TH;
+  out[HONK_CONV3X3_PLAN_WGRAD_NBAND] = p.wg.g.nband;
+  out[HONK_CONV3X3_PLAN_WGRAD_GRID] = p.wg.grid;
+  out[HONK_CONV3X3_PLAN_FOLD] = p.fold;
+  return HONK_OK;
+}
+
 extern "C" int honk_conv3x3_f32(const float* x, const float* w, float* y, int64_t batch, int32_t c, int32_t h,
                                 int32_t w_, int32_t dil, int32_t flip, void* stream) {
   int rc = tc_check(x, w, y, batch, c, h, w_, dil);
@@ -2132,59 +2238,29 @@ extern "C" int honk_conv3x3_f32(const float* x, const float* w, float* y, int64_
   train::Conv3Args a;
   a.x = x; a.w = w; a.y = y;
   a.B = (int)batch; a.H = h; a.W = w_; a.flip = flip ? 1 : 0;
-  a.g = train::class_bands(h, dil, train::tc_rows(c, h, w_, dil, true));
-  const int grid = train::tc_grid((int64_t)a.B * a.g.nband);
+  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());
+  a.g = cp.g;
+  const int grid = cp.grid;
   hipStream_t st = (hipStream_t)stream;
   TimedLaunch tl(st, 2.0 * (double)batch * h * w_ * c * c * 9);
-  const int np = (int)cdiv((int64_t)a.g.TH * w_, 256);  // output pixels per thread
-  // 19 maps: the LDS-DMA double-buffered MFMA kernel where it applies (d <= 4, W % 4 == 0),
-  // else the register-staged one; HONK_TRAIN_CONV=m / v forces conv3x3m / the VALU kernel
-  // (tests compare all three bitwise)
-  const char* ke = getenv("HONK_TRAIN_CONV");
-  const int tdr = c == 19 && !(ke && (ke[0] == 'v' || ke[0] == 'm')) ? train::td_rows(c, h, w_, dil) : 0;
-  if (tdr > 0) {
-    a.g = train::class_bands(h, dil, tdr);
-    const int gd = (int)std::min<int64_t>((int64_t)a.B * a.g.nband, cu_count());
-    if (train::td_fixed(a)) hipLaunchKernelGGL((train::conv3x3d_kernel<19, 0, 20, 1, 25>), dim3(gd), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((train::conv3x3d_kernel<19, 0>), dim3(gd), dim3(512), 0, st, a);
-  } else if (c == 19 && !(ke && ke[0] == 'v') && train::tm_rows(c, h, w_, dil) > 0) {
-    a.g = train::class_bands(h, dil, train::tm_rows(c, h, w_, dil));
-    const int gm = train::tc_grid((int64_t)a.B * a.g.nband);
-    hipLaunchKernelGGL((train::conv3x3m_kernel<19>), dim3(gm), dim3(256), 0, st, a);
+  if (cp.family == train::FAM_DMA) {
+    if (cp.fixed) hipLaunchKernelGGL((train::conv3x3d_kernel<19, 0, 20, 1, 25>), dim3(grid), dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((train::conv3x3d_kernel<19, 0>), dim3(grid), dim3(512), 0, st, a);
+  } else if (cp.family == train::FAM_MFMA) {
+    hipLaunchKernelGGL((train::conv3x3m_kernel<19>), dim3(grid), dim3(256), 0, st, a);
   } else if (c == 19) {
-    if (np <= 1) hipLaunchKernelGGL((train::conv3x3_kernel<19, 1>), dim3(grid), dim3(256), 0, st, a);
-    else if (np == 2) hipLaunchKernelGGL((train::conv3x3_kernel<19, 2>), dim3(grid), dim3(256), 0, st, a);
-    else if (np == 3) hipLaunchKernelGGL((train::conv3x3_kernel<19, 3>), dim3(grid), dim3(256), 0, st, a);
+    if (cp.np == 1) hipLaunchKernelGGL((train::conv3x3_kernel<19, 1>), dim3(grid), dim3(256), 0, st, a);
+    else if (cp.np == 2) hipLaunchKernelGGL((train::conv3x3_kernel<19, 2>), dim3(grid), dim3(256), 0, st, a);
+    else if (cp.np == 3) hipLaunchKernelGGL((train::conv3x3_kernel<19, 3>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((train::conv3x3_kernel<19, 4>), dim3(grid), dim3(256), 0, st, a);
   } else {
-    if (np <= 1) hipLaunchKernelGGL((train::conv3x3_kernel<45, 1>), dim3(grid), dim3(256), 0, st, a);
+    if (cp.np == 1) hipLaunchKernelGGL((train::conv3x3_kernel<45, 1>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((train::conv3x3_kernel<45, 2>), dim3(grid), dim3(256), 0, st, a);
   }
   tl.done(st);
   HONK_LAUNCH_CHECK("conv3x3_kernel");
   return HONK_OK;
 }
-
-namespace {
-// the weight-gradient kernel for a shape: the MFMA one for 19 maps (HONK_TRAIN_CONV=v
-// selects the VALU kernel, for tests), its class-band geometry and grid
-struct WgradPlan {
-  bool mfma, dma;
-  train::ClassBands g;
-  int grid;
-};
-WgradPlan wgrad_plan(int64_t batch, int c, int h, int w_, int dil) {
-  WgradPlan p;
-  const char* ke = getenv("HONK_TRAIN_CONV");
-  const int td = c == 19 && !(ke && (ke[0] == 'v' || ke[0] == 'm')) ? train::twd_rows(c, h, w_, dil) : 0;
-  const int tw = c == 19 && !(ke && ke[0] == 'v') ? train::tw_rows(c, h, w_, dil) : 0;
-  p.dma = td > 0;
-  p.mfma = !p.dma && tw > 0;
-  p.g = train::class_bands(h, dil, p.dma ? td : p.mfma ? tw : train::tc_rows(c, h, w_, dil));
-  p.grid = p.dma ? (int)std::min<int64_t>(batch * p.g.nband, cu_count()) : train::tc_grid(batch * p.g.nband);
-  return p;
-}
-}  // namespace
 
 extern "C" size_t honk_conv3x3_wgrad_workspace_bytes(int64_t batch, int32_t c, int32_t h, int32_t w_, int32_t dil) {
   if (batch < 1 || (c != 19 && c != 45) || h < 1 || w_ < 1 || dil < 1 || dil > 64) return 0;
@@ -2196,7 +2272,7 @@ extern "C" size_t honk_conv3x3_wgrad_workspace_bytes(int64_t batch, int32_t c, i
   if (tw > 0) t = std::max<int64_t>(t, batch * train::class_bands(h, dil, tw).nband);
   const int td = c == 19 ? train::twd_rows(c, h, w_, dil) : 0;  // grid <= CUs < tc_grid's 2 CUs
   if (td > 0) t = std::max<int64_t>(t, batch * train::class_bands(h, dil, td).nband);
-  return (size_t)train::tc_grid(t) * c * c * 9 * sizeof(float);
+  return (size_t)train::tc_grid(t, cu_count()) * c * c * 9 * sizeof(float);
 }
 
 namespace {
@@ -2216,24 +2292,21 @@ int conv3x3_wgrad(const float* x, const float* dy, float* dw, int64_t batch, int
   a.x = x; a.dy = dy; a.part = (float*)workspace;
   a.B = (int)batch; a.H = h; a.W = w_;
   a.fm = fm; a.fi = fi;
-  const WgradPlan wp = wgrad_plan(batch, c, h, w_, dil);
-  if (fm && !wp.dma) return fail(HONK_ERR_UNSUPPORTED, "conv3x3 wgrad: folded BatchNorm needs the DMA-staged kernels");
+  const train::WgradPlan wp = train::wgrad_plan(batch, c, h, w_, dil, cu_count());
+  const bool dma = wp.family == train::FAM_DMA;
+  if (fm && !dma) return fail(HONK_ERR_UNSUPPORTED, "conv3x3 wgrad: folded BatchNorm needs the DMA-staged kernels");
   a.g = wp.g;
   const int grid = wp.grid;
   TimedLaunch tl(st, 2.0 * (double)batch * h * w_ * c * c * 9);
-  // HONK_WGRAD=d: wgrad3x3d_kernel instead of wgrad3x3q_kernel (A/B, tests)
-  const char* we = getenv("HONK_WGRAD");
-  const bool wq = !(we && we[0] == 'd');
-  const bool wh = we && we[0] == 'h';  // HONK_WGRAD=h: the hybrid (16x16x4 for outputs 0..15)
-  if (wp.dma && wq && wh && train::twd_fixed(a))
+  if (dma && wp.variant == 'h' && wp.fixed)
     hipLaunchKernelGGL((train::wgrad3x3q_kernel<19, true, 20, 1, 17>), dim3(grid), dim3(512), 0, st, a);
-  else if (wp.dma && wq && wh) hipLaunchKernelGGL((train::wgrad3x3q_kernel<19, true>), dim3(grid), dim3(512), 0, st, a);
-  else if (wp.dma && wq && train::twd_fixed(a))
+  else if (dma && wp.variant == 'h') hipLaunchKernelGGL((train::wgrad3x3q_kernel<19, true>), dim3(grid), dim3(512), 0, st, a);
+  else if (dma && wp.variant == 'q' && wp.fixed)
     hipLaunchKernelGGL((train::wgrad3x3q_kernel<19, false, 20, 1, 17>), dim3(grid), dim3(512), 0, st, a);
-  else if (wp.dma && wq) hipLaunchKernelGGL((train::wgrad3x3q_kernel<19, false>), dim3(grid), dim3(512), 0, st, a);
-  else if (wp.dma && train::twd_fixed(a)) hipLaunchKernelGGL((train::wgrad3x3d_kernel<19, 20, 1, 17>), dim3(grid), dim3(512), 0, st, a);
-  else if (wp.dma) hipLaunchKernelGGL((train::wgrad3x3d_kernel<19>), dim3(grid), dim3(512), 0, st, a);
-  else if (wp.mfma) hipLaunchKernelGGL((train::wgrad3x3m_kernel<19>), dim3(grid), dim3(256), 0, st, a);
+  else if (dma && wp.variant == 'q') hipLaunchKernelGGL((train::wgrad3x3q_kernel<19, false>), dim3(grid), dim3(512), 0, st, a);
+  else if (dma && wp.fixed) hipLaunchKernelGGL((train::wgrad3x3d_kernel<19, 20, 1, 17>), dim3(grid), dim3(512), 0, st, a);
+  else if (dma) hipLaunchKernelGGL((train::wgrad3x3d_kernel<19>), dim3(grid), dim3(512), 0, st, a);
+  else if (wp.family == train::FAM_MFMA) hipLaunchKernelGGL((train::wgrad3x3m_kernel<19>), dim3(grid), dim3(256), 0, st, a);
   else if (c == 19) hipLaunchKernelGGL((train::wgrad3x3_kernel<19>), dim3(grid), dim3(512), 0, st, a);
   else hipLaunchKernelGGL((train::wgrad3x3_kernel<45>), dim3(grid), dim3(512), 0, st, a);
   tl.done(st);
@@ -2393,20 +2466,18 @@ extern "C" int honk_res_tail_bwd_f32(const float* gy, const float* gs, const flo
 // its partial sums instead of their own pass over the tensors ----
 namespace {
 int stats_grid(int64_t batch, int c, int h, int w_, int dil) {
-  if (batch < 1 || c != 19 || h < 1 || w_ < 1 || dil < 1 || dil > 64) return 0;
-  const char* ke = getenv("HONK_TRAIN_CONV");
-  if (ke && (ke[0] == 'v' || ke[0] == 'm')) return 0;
-  const int tdr = train::td_rows(c, h, w_, dil);
-  if (tdr <= 0) return 0;
-  return (int)std::min<int64_t>(batch * train::class_bands(h, dil, tdr).nband, cu_count());
+  if (batch < 1 || c != 19 || !train::plan_shape_ok(c, h, w_, dil)) return 0;
+  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());
+  return cp.family == train::FAM_DMA ? cp.grid : 0;
 }
 }  // namespace
 
 namespace {
 // conv3x3d_kernel with the statistics epilogue: mode 1 / 2, the fixed-geometry instance
 // where it applies, the folded-BatchNorm instance when a.fm is set
-void launch_conv_stats(const train::Conv3Args& a, int mode, int S, hipStream_t st) {
-  const bool fx = train::td_fixed(a), fo = a.fm != nullptr;
+void launch_conv_stats(const train::Conv3Args& a, int mode, const train::ConvPlan& cp, hipStream_t st) {
+  const bool fx = cp.fixed, fo = a.fm != nullptr;
+  const int S = cp.grid;
 #define HONK_CS(M, FO)                                                                                           \
   if (fx) hipLaunchKernelGGL((train::conv3x3d_kernel<19, M, 20, 1, 25, FO>), dim3(S), dim3(512), 0, st, a); \
   else hipLaunchKernelGGL((train::conv3x3d_kernel<19, M, 0, 0, 0, FO>), dim3(S), dim3(512), 0, st, a);
@@ -2440,14 +2511,15 @@ extern "C" int honk_conv3x3_stats_bn_f32(const float* x, const float* w, float* 
   train::Conv3Args a;
   a.x = x; a.w = w; a.y = y;
   a.B = (int)batch; a.H = h; a.W = w_; a.flip = flip ? 1 : 0;
-  a.g = train::class_bands(h, dil, train::td_rows(c, h, w_, dil));
+  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());  // (S > 0: the DMA family)
+  a.g = cp.g;
   a.aux = aux;
   a.part = (double*)stats;
   a.mask = nullptr;
   a.fm = fold_mean; a.fi = fold_invstd;
   hipStream_t st = (hipStream_t)stream;
   TimedLaunch tl(st, 2.0 * (double)batch * h * w_ * c * c * 9);
-  launch_conv_stats(a, mode, S, st);
+  launch_conv_stats(a, mode, cp, st);
   tl.done(st);
   HONK_LAUNCH_CHECK("conv3x3d_kernel");
   return HONK_OK;
@@ -2476,14 +2548,15 @@ extern "C" int honk_conv3x3_tail_bn_f32(const float* x, const float* w, float* s
   train::Conv3Args a;
   a.x = x; a.w = w; a.y = s;
   a.B = (int)batch; a.H = h; a.W = w_; a.flip = 0;
-  a.g = train::class_bands(h, dil, train::td_rows(c, h, w_, dil));
+  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());  // (S > 0: the DMA family)
+  a.g = cp.g;
   a.aux = old;
   a.part = (double*)stats;
   a.mask = mask;
   a.fm = fold_mean; a.fi = fold_invstd;
   hipStream_t st = (hipStream_t)stream;
   TimedLaunch tl(st, 2.0 * (double)batch * h * w_ * c * c * 9);
-  launch_conv_stats(a, 1, S, st);
+  launch_conv_stats(a, 1, cp, st);
   tl.done(st);
   HONK_LAUNCH_CHECK("conv3x3d_kernel (tail epilogue)");
   return HONK_OK;
@@ -2497,7 +2570,7 @@ extern "C" int honk_conv3x3_tail_f32(const float* x, const float* w, float* s, u
 }
 
 extern "C" int honk_conv3x3_bn_fold_check(int64_t batch, int32_t c, int32_t h, int32_t w_, int32_t dil) {
-  if (stats_grid(batch, c, h, w_, dil) <= 0 || !wgrad_plan(batch, c, h, w_, dil).dma)
+  if (stats_grid(batch, c, h, w_, dil) <= 0 || !train::plan(batch, c, h, w_, dil, cu_count()).fold)
     return fail(HONK_ERR_UNSUPPORTED, "conv3x3: no folded BatchNorm for this shape");
   return HONK_OK;
 }

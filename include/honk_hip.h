@@ -394,6 +394,37 @@ int honk_conv3x3_f32(const float* x, const float* w, float* y, int64_t batch, in
 /* Host-only: HONK_OK when honk_conv3x3_f32 / honk_conv3x3_wgrad_f32 cover (C, H, W, dil),
  * else the status (and honk_last_error text) those calls would return. */
 int honk_conv3x3_check(int32_t c, int32_t h, int32_t w_, int32_t dil);
+/*
+ * Host-only: which kernels honk_conv3x3_f32 (forward / input gradient) and
+ * honk_conv3x3_wgrad_f32 run `batch` clips of (C, H, W, dil) on, under the current
+ * environment (HONK_TRAIN_CONV, HONK_WGRAD, HONK_TD_FIXED), as out[HONK_CONV3X3_PLAN_COUNT].
+ * The launches read the same plan.  n_cus = 0: the current device's CU count.  A shape
+ * honk_conv3x3_check refuses as unsupported gives HONK_OK with every entry 0 (the callers
+ * run it on honk_conv_same_f32); HONK_ERR_ARG as honk_conv3x3_f32, and for batch < 1.
+ * STATS: honk_conv3x3_stats_f32 / _tail_f32 take the shape (honk_conv3x3_stats_bytes > 0);
+ * FOLD: honk_conv3x3_bn_fold_check.  A tile is TH rows of one dilation class of one clip at
+ * full width, NBAND tiles per clip; a workgroup walks the tiles blockIdx.x, + GRID, ...
+ */
+#define HONK_CONV3X3_FAMILY_DMA 1  /* LDS-DMA staged fp32 MFMA: conv3x3d_kernel, wgrad3x3q/d_kernel */
+#define HONK_CONV3X3_FAMILY_MFMA 2 /* register-staged fp32 MFMA: conv3x3m_kernel, wgrad3x3m_kernel  */
+#define HONK_CONV3X3_FAMILY_VALU 3 /* conv3x3_kernel<C, NP>, wgrad3x3_kernel<C>                     */
+#define HONK_CONV3X3_PLAN_OK 0            /* the dedicated kernels take the shape                  */
+#define HONK_CONV3X3_PLAN_CONV_FAMILY 1
+#define HONK_CONV3X3_PLAN_CONV_NP 2       /* VALU: output pixels per thread, else 0                */
+#define HONK_CONV3X3_PLAN_CONV_FIXED 3    /* the compile-time 20-wide, 25-row instance             */
+#define HONK_CONV3X3_PLAN_CONV_TH 4
+#define HONK_CONV3X3_PLAN_CONV_NBAND 5
+#define HONK_CONV3X3_PLAN_CONV_GRID 6
+#define HONK_CONV3X3_PLAN_STATS 7
+#define HONK_CONV3X3_PLAN_WGRAD_FAMILY 8
+#define HONK_CONV3X3_PLAN_WGRAD_VARIANT 9 /* DMA: 'q', 'h' or 'd' (HONK_WGRAD), else 0             */
+#define HONK_CONV3X3_PLAN_WGRAD_FIXED 10  /* the compile-time 20-wide, 17-row instance             */
+#define HONK_CONV3X3_PLAN_WGRAD_TH 11
+#define HONK_CONV3X3_PLAN_WGRAD_NBAND 12
+#define HONK_CONV3X3_PLAN_WGRAD_GRID 13
+#define HONK_CONV3X3_PLAN_FOLD 14
+#define HONK_CONV3X3_PLAN_COUNT 16
+int honk_conv3x3_plan(int64_t batch, int32_t c, int32_t h, int32_t w_, int32_t dil, int32_t n_cus, int32_t* out);
 /* dw[o][i][ky][kx] = sum_{b,h,w} dy[b][o][h][w] * x[b][i][h+(ky-1)d][w+(kx-1)d] (zero padded);
  * deterministic: per-workgroup partials in the workspace, summed in a fixed order. */
 size_t honk_conv3x3_wgrad_workspace_bytes(int64_t batch, int32_t c, int32_t h, int32_t w_, int32_t dil);
