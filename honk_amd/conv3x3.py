@@ -16,6 +16,7 @@ loop (train.py:131-134) runs unchanged.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import os
 
@@ -63,9 +64,18 @@ def _dedicated_wgrad(C, H, W, d) -> bool:
     return _dedicated(C, H, W, d)
 
 
+def _ws(nbytes, device):
+    """A device workspace of nbytes (never empty: an empty tensor's data_ptr() is null)."""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def _same_ws(B, C, H, W, d, device):
     n = int(_native.load().honk_conv_same_workspace_bytes(B, C, H, W, d))
-    return torch.empty(max(n, 1), dtype=torch.uint8, device=device), n
+    return _ws(n, device), n
 
 
 def warn_fallback(model, what, phase="training"):
@@ -102,33 +112,52 @@ def _conv(x, w, flip, d=1):
     return y
 
 
-def _wgrad(x, dy, d=1):
+def _wgrad(x, dy, d=1, fold=None):
+    """fold = (mean, invstd): x holds the layer below's s and the conv's input is its
+    BatchNorm (honk_conv3x3_wgrad_bn_f32, the dedicated kernels only)."""
     x, dy = x.contiguous(), dy.contiguous()
     B, C, H, W = x.shape
     lib = _native.load()
     dw = torch.empty(C, C, 3, 3, dtype=torch.float32, device=x.device)
-    if _dedicated_wgrad(C, H, W, d):
-        nbytes = lib.honk_conv3x3_wgrad_workspace_bytes(B, C, H, W, d)
-        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=x.device)
-        _native.check(lib.honk_conv3x3_wgrad_f32(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, C, H, W, d,
-                                                 ws.data_ptr(), nbytes, _native.stream_handle(x.device)),
-                      "honk_conv3x3_wgrad_f32")
+    st = _native.stream_handle(x.device)
+    if fold is not None or _dedicated_wgrad(C, H, W, d):
+        nb = int(lib.honk_conv3x3_wgrad_workspace_bytes(B, C, H, W, d))
+        ws = _ws(nb, x.device)
+        if fold is not None:
+            _native.check(lib.honk_conv3x3_wgrad_bn_f32(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, C, H, W, d,
+                                                        fold[0].data_ptr(), fold[1].data_ptr(), ws.data_ptr(), nb, st),
+                          "honk_conv3x3_wgrad_bn_f32")
+        else:
+            _native.check(lib.honk_conv3x3_wgrad_f32(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, C, H, W, d,
+                                                     ws.data_ptr(), nb, st), "honk_conv3x3_wgrad_f32")
         return dw
     ws, nb = _same_ws(B, C, H, W, d, x.device)
     _native.check(lib.honk_conv_same_wgrad_f32(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, C, H, W, d,
-                                               ws.data_ptr(), nb, _native.stream_handle(x.device)),
-                  "honk_conv_same_wgrad_f32")
+                                               ws.data_ptr(), nb, st), "honk_conv_same_wgrad_f32")
     return dw
 
 
 STATS_USED = {"fwd": 0, "bwd": 0}   # tails that took the conv epilogue's statistics (tests)
 FOLD_USED = {"n": 0}   # convs that took the layer below's BatchNorm folded in (tests)
 
+# what the convs leave in a statistics box for the tails: box["fwd"] (the forward conv's
+# epilogue: partials laid out by its grid, so by its dilation) and box["bwd"] (the input-
+# gradient conv's: the statistics of dx as it was, at that version, when the conv returned it)
+FwdStats = collections.namedtuple("FwdStats", "buf dil")
+BwdStats = collections.namedtuple("BwdStats", "buf dx version dil")
+
 
 def _stats_buf(B, C, H, W, d, device):
     """The statistics buffer of the conv epilogue for this shape, or None (no epilogue)."""
     n = int(_native.load().honk_conv3x3_stats_bytes(B, C, H, W, d))
-    return torch.empty(n, dtype=torch.uint8, device=device) if n else None
+    return _ws(n, device) if n else None
+
+
+def _summed_by_conv(box, gy):
+    """The box's "bwd" entry (taken out of the box) if the conv that produced exactly this
+    gradient summed its statistics, else None."""
+    pre = box.pop("bwd", None) if box is not None else None
+    return pre if pre is not None and pre.dx is gy and gy._version == pre.version else None
 
 
 def _conv_stats(x, w, flip, d, mode, aux, buf, fold=None):
@@ -137,27 +166,11 @@ def _conv_stats(x, w, flip, d, mode, aux, buf, fold=None):
     x = x.contiguous()
     B, C, H, W = x.shape
     y = torch.empty_like(x)
-    fm, fi = (fold[0].data_ptr(), fold[1].data_ptr()) if fold is not None else (None, None)
+    fm, fi = fold if fold is not None else (None, None)
     _native.check(_native.load().honk_conv3x3_stats_bn_f32(
-        x.data_ptr(), w.data_ptr(), y.data_ptr(), B, C, H, W, d, 1 if flip else 0, mode,
-        aux.data_ptr() if aux is not None else None, fm, fi, buf.data_ptr(), buf.numel(),
-        _native.stream_handle(x.device)), "honk_conv3x3_stats_bn_f32")
+        x.data_ptr(), w.data_ptr(), y.data_ptr(), B, C, H, W, d, 1 if flip else 0, mode, _ptr(aux), _ptr(fm),
+        _ptr(fi), buf.data_ptr(), buf.numel(), _native.stream_handle(x.device)), "honk_conv3x3_stats_bn_f32")
     return y
-
-
-def _wgrad_fold(xs, dy, d, fold):
-    """The weight gradient of a conv whose input is BatchNorm(xs) (xs = the layer
-    below's s, fold = its (mean, invstd)): honk_conv3x3_wgrad_bn_f32."""
-    dy = dy.contiguous()
-    B, C, H, W = xs.shape
-    lib = _native.load()
-    dw = torch.empty(C, C, 3, 3, dtype=torch.float32, device=xs.device)
-    nbytes = lib.honk_conv3x3_wgrad_workspace_bytes(B, C, H, W, d)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=xs.device)
-    _native.check(lib.honk_conv3x3_wgrad_bn_f32(xs.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, C, H, W, d,
-                                                fold[0].data_ptr(), fold[1].data_ptr(), ws.data_ptr(), nbytes,
-                                                _native.stream_handle(xs.device)), "honk_conv3x3_wgrad_bn_f32")
-    return dw
 
 
 FUSE_TAIL = os.environ.get("HONK_TRAIN_FUSE_TAIL", "1") != "0"   # tests compare both
@@ -178,12 +191,12 @@ def fold_supported(h, d_next) -> bool:
 class _Conv3x3(torch.autograd.Function):
     """h = conv(x, w).  Statistics boxes (dicts shared with honk_amd's res tails, see
     res_tail): box_out -> this conv's epilogue also sums the next tail's forward
-    statistics (of relu(h) [+ old]) into box_out["fwd"], and (FUSE_TAIL) writes the
+    statistics (of relu(h) [+ old]) into box_out["fwd"] (FwdStats), and (FUSE_TAIL) writes the
     tail's s = relu(h) [+ old] in place of h plus the ReLU bit mask (box_out["mask"]): the
     returned tensor then holds s, which only the tail reads (autograd still sees h: the
     gradient it hands back is the tail's gh); box_in (the box of the tail whose output x
     is) -> the input-gradient conv sums that tail's backward statistics (of dx and
-    dx * x) into box_in["bwd"] = (buffer, dx).  box_in["fold"] = (s, mean, invstd): that
+    dx * x) into box_in["bwd"] (BwdStats).  box_in["fold"] = (s, mean, invstd): that
     tail folded its BatchNorm into this conv -- x is a placeholder of y's shape (never
     read) and the kernels read y = (s - mean) * invstd from s."""
 
@@ -191,56 +204,37 @@ class _Conv3x3(torch.autograd.Function):
     def forward(ctx, x, w, d, old, box_out, box_in):
         w = w.contiguous()
         fold = box_in.pop("fold", None) if box_in is not None else None
-        ctx.fold = fold is not None
+        fm = fi = None
         if fold is not None:
-            xs, fm, fi = fold
-            ctx.save_for_backward(xs, w, fm, fi)
-        else:
-            ctx.save_for_backward(x, w)
+            x, fm, fi = fold   # x: the layer below's s
+            FOLD_USED["n"] += 1
+        ctx.fold = fold is not None
+        ctx.save_for_backward(x, w, *((fm, fi) if fold is not None else ()))
         ctx.dil = d
         ctx.box_in = box_in
-        if fold is not None:
-            FOLD_USED["n"] += 1
-            if box_out is None or not FUSE_TAIL:
-                raise RuntimeError("honk_amd: a folded BatchNorm needs the fused tail epilogue")
-            B, C, H, W = xs.shape
-            buf = _stats_buf(B, C, H, W, d, xs.device)
-            box_out["fwd"] = (buf, d)
-            oc = old.contiguous() if old is not None else None
-            s = torch.empty_like(xs)
-            mask = torch.empty(B, H, W, dtype=torch.int32, device=xs.device)
-            _native.check(_native.load().honk_conv3x3_tail_bn_f32(
-                xs.data_ptr(), w.data_ptr(), s.data_ptr(), mask.data_ptr(), B, C, H, W, d,
-                oc.data_ptr() if oc is not None else None, fm.data_ptr(), fi.data_ptr(), buf.data_ptr(), buf.numel(),
-                _native.stream_handle(xs.device)), "honk_conv3x3_tail_bn_f32")
-            box_out["mask"] = mask
-            return s
-        if box_out is not None:
-            B, C, H, W = x.shape
-            buf = _stats_buf(B, C, H, W, d, x.device)
-            if buf is not None:
-                box_out["fwd"] = (buf, d)   # partials laid out by this conv's grid (its dilation)
-                oc = old.contiguous() if old is not None else None
-                if FUSE_TAIL:
-                    x = x.contiguous()
-                    s = torch.empty_like(x)
-                    mask = torch.empty(B, H, W, dtype=torch.int32, device=x.device)  # bit o: channel o
-                    _native.check(_native.load().honk_conv3x3_tail_f32(
-                        x.data_ptr(), w.data_ptr(), s.data_ptr(), mask.data_ptr(), B, C, H, W, d,
-                        oc.data_ptr() if oc is not None else None, buf.data_ptr(), buf.numel(),
-                        _native.stream_handle(x.device)), "honk_conv3x3_tail_f32")
-                    box_out["mask"] = mask
-                    return s
-                return _conv_stats(x, w, False, d, 1, oc, buf)
-        return _conv(x, w, flip=False, d=d)
+        B, C, H, W = x.shape
+        buf = _stats_buf(B, C, H, W, d, x.device) if box_out is not None else None
+        if fold is not None and (buf is None or not FUSE_TAIL):
+            raise RuntimeError("honk_amd: a folded BatchNorm needs the fused tail epilogue")
+        if buf is None:
+            return _conv(x, w, flip=False, d=d)
+        box_out["fwd"] = FwdStats(buf, d)
+        oc = old.contiguous() if old is not None else None
+        if not FUSE_TAIL:
+            return _conv_stats(x, w, False, d, 1, oc, buf)
+        x = x.contiguous()
+        s = torch.empty_like(x)
+        mask = torch.empty(B, H, W, dtype=torch.int32, device=x.device)  # bit o: channel o
+        _native.check(_native.load().honk_conv3x3_tail_bn_f32(
+            x.data_ptr(), w.data_ptr(), s.data_ptr(), mask.data_ptr(), B, C, H, W, d, _ptr(oc), _ptr(fm), _ptr(fi),
+            buf.data_ptr(), buf.numel(), _native.stream_handle(x.device)), "honk_conv3x3_tail_bn_f32")
+        box_out["mask"] = mask
+        return s
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.fold:
-            x, w, fm, fi = ctx.saved_tensors   # x: the layer below's s
-            fold = (fm, fi)
-        else:
-            (x, w), fold = ctx.saved_tensors, None
+        x, w = ctx.saved_tensors[:2]   # (fold: x is the layer below's s)
+        fold = ctx.saved_tensors[2:] if ctx.fold else None
         dy = dy.contiguous()
         dx = None
         if ctx.needs_input_grad[0]:
@@ -249,15 +243,12 @@ class _Conv3x3(torch.autograd.Function):
             buf = _stats_buf(B, C, H, W, ctx.dil, x.device) if box is not None else None
             if buf is not None:
                 dx = _conv_stats(dy, w, True, ctx.dil, 2, x.contiguous(), buf, fold)
-                box["bwd"] = (buf, dx, dx._version, ctx.dil)
+                box["bwd"] = BwdStats(buf, dx, dx._version, ctx.dil)
             elif fold is not None:
                 raise RuntimeError("honk_amd: a folded BatchNorm needs the input-gradient statistics epilogue")
             else:
                 dx = _conv(dy, w, flip=True, d=ctx.dil)
-        if ctx.needs_input_grad[1]:
-            dw = _wgrad_fold(x, dy, ctx.dil, fold) if fold is not None else _wgrad(x, dy, d=ctx.dil)
-        else:
-            dw = None
+        dw = _wgrad(x, dy, ctx.dil, fold) if ctx.needs_input_grad[1] else None
         return dx, dw, None, None, None, None
 
 
@@ -267,8 +258,8 @@ def conv3x3(x, w, d=1, old=None, box_out=None, box_in=None):
 
 # -- train-mode BatchNorm2d(affine=False) (model.py:100, 117-118 in training) -------
 def _bn_ws(B, C, HW, device):
-    n = _native.load().honk_bn_train_workspace_bytes(B, C, HW)
-    return torch.empty(max(int(n), 1), dtype=torch.uint8, device=device), int(n)
+    n = int(_native.load().honk_bn_train_workspace_bytes(B, C, HW))
+    return _ws(n, device), n
 
 
 class _BatchNormTrain(torch.autograd.Function):
@@ -280,12 +271,9 @@ class _BatchNormTrain(torch.autograd.Function):
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
         ws, nb = _bn_ws(B, C, H * W, x.device)
-        rm = running_mean.data_ptr() if running_mean is not None else None
-        rv = running_var.data_ptr() if running_var is not None else None
-        _native.check(_native.load().honk_bn_train_fwd_f32(x.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                           invstd.data_ptr(), rm, rv, B, C, H * W, momentum, eps,
-                                                           ws.data_ptr(), nb, _native.stream_handle(x.device)),
-                      "honk_bn_train_fwd_f32")
+        _native.check(_native.load().honk_bn_train_fwd_f32(
+            x.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(running_mean), _ptr(running_var),
+            B, C, H * W, momentum, eps, ws.data_ptr(), nb, _native.stream_handle(x.device)), "honk_bn_train_fwd_f32")
         ctx.save_for_backward(y, invstd)
         return y
 
@@ -316,63 +304,46 @@ class _ResTail(torch.autograd.Function):
         B, C, H, W = h.shape
         mean = torch.empty(C, dtype=torch.float32, device=h.device)
         invstd = torch.empty_like(mean)
-        ptr = (lambda t: t.data_ptr() if t is not None else None)
-        st = _native.stream_handle(h.device)
+        lib, st = _native.load(), _native.stream_handle(h.device)
+        bn = (mean.data_ptr(), invstd.data_ptr(), _ptr(running_mean), _ptr(running_var))
         mask = box.pop("mask", None) if box is not None else None
+        pre = box.pop("fwd") if box is not None and (mask is not None or "fwd" in box) else None
         # fold (only on the masked path, whose conv epilogue supplied the statistics): no y --
         # a zero-storage placeholder of its shape (a stray read sees one element, not a stale
         # full-size buffer, and nothing is allocated); every other path writes a full y
         fold = bool(fold) and mask is not None
         y = torch.empty((), dtype=h.dtype, device=h.device).expand(B, C, H, W) if fold else torch.empty_like(h)
-        if mask is not None:
-            # h holds s = relu(h) [+ old] from the conv's epilogue (and old was read there)
+        s = h if mask is not None else torch.empty_like(h) if keep_s else None
+        if pre is not None:
             STATS_USED["fwd"] += 1
-            buf, d = box.pop("fwd")
-            # fold: no y -- the next conv reads (s - mean) * invstd from s (box["fold"]);
-            # the returned y is a placeholder of its shape that nothing reads
-            with _synced(buf):
-                _native.check(_native.load().honk_res_tail_fwd_s_f32(
-                    h.data_ptr(), None if fold else y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                    ptr(running_mean), ptr(running_var), buf.data_ptr(), B, C, H, W, d, momentum, eps, st),
-                    "honk_res_tail_fwd_s_f32")
+        if mask is not None:
+            # the conv's epilogue summed the statistics and wrote s = relu(h) [+ old] in place of h
+            # (old was read there).  fold: no y -- the next conv reads (s - mean) * invstd from s
+            with _synced(pre.buf):
+                _native.check(lib.honk_res_tail_fwd_s_f32(h.data_ptr(), None if fold else y.data_ptr(), *bn,
+                                                          pre.buf.data_ptr(), B, C, H, W, pre.dil, momentum, eps, st),
+                              "honk_res_tail_fwd_s_f32")
             if fold:
                 box["fold"] = (h, mean, invstd)
-                ctx.save_for_backward(mask, h, invstd, mean)
-            else:
-                ctx.save_for_backward(mask, y, invstd)
-            ctx.fold = bool(fold)
-            ctx.has_old = old is not None
-            ctx.box = box
-            ctx.masked = True
-            if keep_s:
-                return y, h
-            return y
-        s = torch.empty_like(h) if keep_s else None
-        if box is not None and "fwd" in box:
-            STATS_USED["fwd"] += 1
-            buf, d = box.pop("fwd")
-            with _synced(buf):
-                _native.check(_native.load().honk_res_tail_fwd_part_f32(
-                    h.data_ptr(), ptr(old), ptr(s), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                    ptr(running_mean), ptr(running_var), buf.data_ptr(), B, C, H, W, d, momentum, eps, st),
-                    "honk_res_tail_fwd_part_f32")
-        else:
+        elif pre is not None:   # the conv's epilogue summed the statistics; h is the conv's output
+            with _synced(pre.buf):
+                _native.check(lib.honk_res_tail_fwd_part_f32(h.data_ptr(), _ptr(old), _ptr(s), y.data_ptr(), *bn,
+                                                             pre.buf.data_ptr(), B, C, H, W, pre.dil, momentum, eps,
+                                                             st), "honk_res_tail_fwd_part_f32")
+        else:   # the tail's own pass over h
             if syncbn.active():
                 raise RuntimeError("honk_amd: SyncBN needs the conv epilogue's statistics (model.py routes "
                                    "other shapes to syncbn.batch_norm)")
             ws, nb = _bn_ws(B, C, H * W, h.device)
-            _native.check(_native.load().honk_res_tail_fwd_f32(h.data_ptr(), ptr(old), ptr(s), y.data_ptr(),
-                                                               mean.data_ptr(), invstd.data_ptr(), ptr(running_mean),
-                                                               ptr(running_var), B, C, H * W, momentum, eps,
-                                                               ws.data_ptr(), nb, st), "honk_res_tail_fwd_f32")
-        ctx.save_for_backward(h, y, invstd)
-        ctx.fold = False
+            _native.check(lib.honk_res_tail_fwd_f32(h.data_ptr(), _ptr(old), _ptr(s), y.data_ptr(), *bn, B, C, H * W,
+                                                    momentum, eps, ws.data_ptr(), nb, st), "honk_res_tail_fwd_f32")
+        # backward reads the ReLU's mask or h, then y -- with a folded BatchNorm the tail's s, and its mean
+        ctx.save_for_backward(h if mask is None else mask, h if fold else y, invstd, *((mean,) if fold else ()))
+        ctx.fold = fold
         ctx.has_old = old is not None
         ctx.box = box
-        ctx.masked = False
-        if keep_s:
-            return y, s
-        return y
+        ctx.masked = mask is not None
+        return (y, s) if keep_s else y
 
     @staticmethod
     def backward(ctx, gy, gs=None):
@@ -384,52 +355,42 @@ class _ResTail(torch.autograd.Function):
         gs = gs.contiguous() if gs is not None else None
         gh = torch.empty_like(y)
         gold = torch.empty_like(y) if ctx.has_old and ctx.needs_input_grad[1] else None
-        ptr = (lambda t: t.data_ptr() if t is not None else None)
-        st = _native.stream_handle(y.device)
-        pre = ctx.box.pop("bwd", None) if ctx.box is not None else None
-        if ctx.masked:
-            if pre is not None and pre[1] is gy and gy._version == pre[2]:
-                STATS_USED["bwd"] += 1
-                buf, dil = pre[0], pre[3]
-            else:  # no input-gradient conv summed this gradient's statistics: the tail does
-                gy = gy.contiguous()
-                buf, _ = _bn_ws(B, C, H * W, y.device)
-                dil = 0
-                if syncbn.active() and not ctx.fold:
-                    # SyncBN: the partials first (all-reduced below), then the tail takes them (dil -1)
-                    _native.check(_native.load().honk_bn_partials_f32(
-                        gy.data_ptr(), y.data_ptr(), buf.data_ptr(), buf.numel(), B, C, H * W, st),
-                        "honk_bn_partials_f32")
-                    dil = -1
-            if ctx.fold:
-                if dil == 0:
-                    raise RuntimeError("honk_amd: a folded BatchNorm's gradient reached the tail without its conv")
-                with _synced(buf):
-                    _native.check(_native.load().honk_res_tail_bwd_mask_bn_f32(
-                        gy.data_ptr(), ptr(gs), y.data_ptr(), ctx.saved_tensors[3].data_ptr(), invstd.data_ptr(),
-                        h.data_ptr(), gh.data_ptr(), ptr(gold), B, C, H, W, dil, buf.data_ptr(), buf.numel(), st),
-                        "honk_res_tail_bwd_mask_bn_f32")
-            else:
-                with _synced(buf if dil != 0 else None):
-                    _native.check(_native.load().honk_res_tail_bwd_mask_f32(
-                        gy.data_ptr(), ptr(gs), y.data_ptr(), invstd.data_ptr(), h.data_ptr(), gh.data_ptr(),
-                        ptr(gold), B, C, H, W, dil, buf.data_ptr(), buf.numel(), st), "honk_res_tail_bwd_mask_f32")
-        elif pre is not None and pre[1] is gy and gy._version == pre[2]:
-            # the statistics of exactly this gradient, summed by the conv that produced it
+        lib, st = _native.load(), _native.stream_handle(y.device)
+        pre = _summed_by_conv(ctx.box, gy)
+        if pre is not None:
             STATS_USED["bwd"] += 1
-            with _synced(pre[0]):
-                _native.check(_native.load().honk_res_tail_bwd_part_f32(
-                    gy.data_ptr(), ptr(gs), y.data_ptr(), invstd.data_ptr(), h.data_ptr(), gh.data_ptr(), ptr(gold),
-                    pre[0].data_ptr(), B, C, H, W, pre[3], st), "honk_res_tail_bwd_part_f32")
-        else:
-            if syncbn.active():
-                raise RuntimeError("honk_amd: SyncBN needs the input-gradient conv's statistics on the unfused tail")
+        elif syncbn.active() and not ctx.masked:
+            raise RuntimeError("honk_amd: SyncBN needs the input-gradient conv's statistics on the unfused tail")
+        else:   # no input-gradient conv summed this gradient's statistics: the tail does
             gy = gy.contiguous()
             ws, nb = _bn_ws(B, C, H * W, y.device)
-            _native.check(_native.load().honk_res_tail_bwd_f32(gy.data_ptr(), ptr(gs), y.data_ptr(),
-                                                               invstd.data_ptr(), h.data_ptr(), gh.data_ptr(),
-                                                               ptr(gold), B, C, H * W, ws.data_ptr(), nb, st),
-                          "honk_res_tail_bwd_f32")
+        if ctx.masked:
+            buf, dil = (pre.buf, pre.dil) if pre is not None else (ws, 0)
+            if pre is None and syncbn.active() and not ctx.fold:
+                # SyncBN: the partials first (all-reduced below), then the tail takes them (dil -1)
+                _native.check(lib.honk_bn_partials_f32(gy.data_ptr(), y.data_ptr(), buf.data_ptr(), buf.numel(), B, C,
+                                                       H * W, st), "honk_bn_partials_f32")
+                dil = -1
+            if ctx.fold and dil == 0:
+                raise RuntimeError("honk_amd: a folded BatchNorm's gradient reached the tail without its conv")
+            tail = (h.data_ptr(), gh.data_ptr(), _ptr(gold), B, C, H, W, dil, buf.data_ptr(), buf.numel(), st)
+            with _synced(buf if dil != 0 else None):
+                if ctx.fold:
+                    _native.check(lib.honk_res_tail_bwd_mask_bn_f32(
+                        gy.data_ptr(), _ptr(gs), y.data_ptr(), ctx.saved_tensors[3].data_ptr(), invstd.data_ptr(),
+                        *tail), "honk_res_tail_bwd_mask_bn_f32")
+                else:
+                    _native.check(lib.honk_res_tail_bwd_mask_f32(gy.data_ptr(), _ptr(gs), y.data_ptr(),
+                                                                 invstd.data_ptr(), *tail), "honk_res_tail_bwd_mask_f32")
+        elif pre is not None:   # the statistics of exactly this gradient, summed by the conv that produced it
+            with _synced(pre.buf):
+                _native.check(lib.honk_res_tail_bwd_part_f32(
+                    gy.data_ptr(), _ptr(gs), y.data_ptr(), invstd.data_ptr(), h.data_ptr(), gh.data_ptr(), _ptr(gold),
+                    pre.buf.data_ptr(), B, C, H, W, pre.dil, st), "honk_res_tail_bwd_part_f32")
+        else:
+            _native.check(lib.honk_res_tail_bwd_f32(gy.data_ptr(), _ptr(gs), y.data_ptr(), invstd.data_ptr(),
+                                                    h.data_ptr(), gh.data_ptr(), _ptr(gold), B, C, H * W,
+                                                    ws.data_ptr(), nb, st), "honk_res_tail_bwd_f32")
         return gh, gold, None, None, None, None, None, None, None
 
 

@@ -2156,19 +2156,49 @@ static WgradPlan wgrad_plan(int64_t batch, int c, int h, int w, int d, int n_cus
   wg.variant = wg.family != FAM_DMA ? 0 : we && we[0] == 'd' ? 'd' : we && we[0] == 'h' ? 'h' : 'q';
   return wg;
 }
+// the statistics epilogue is conv3x3d_kernel's: one partial per workgroup of the DMA conv
+static int plan_stats(const ConvPlan& cv) { return cv.family == FAM_DMA ? cv.grid : 0; }
 static Plan plan(int64_t batch, int c, int h, int w, int d, int n_cus) {
   Plan p;
   p.conv = conv_plan(batch, c, h, w, d, n_cus);
   p.wg = wgrad_plan(batch, c, h, w, d, n_cus);
-  p.stats = p.conv.family == FAM_DMA ? p.conv.grid : 0;
+  p.stats = plan_stats(p.conv);
   p.fold = p.stats > 0 && p.wg.family == FAM_DMA;
   return p;
+}
+// ---- the plan's answers for any (batch, C, H, W, d), at the current device's CU count: 0 /
+// false where the dedicated kernels do not take the shape or there is no clip.
+// The statistics grid (the conv half of the plan is all of it: the tails ask at every call)
+static int stats_grid(int64_t batch, int c, int h, int w, int d) {
+  if (batch < 1 || c != 19 || !plan_shape_ok(c, h, w, d)) return 0;  // (only 19 maps have a DMA family)
+  return plan_stats(conv_plan(batch, c, h, w, d, cu_count()));
+}
+static bool fold_ok(int64_t batch, int c, int h, int w, int d) {
+  return batch >= 1 && c == 19 && plan_shape_ok(c, h, w, d) && plan(batch, c, h, w, d, cu_count()).fold;
+}
+// The most tiles any weight-gradient family makes of the shape (0: none takes it).  A
+// workspace is sized for this, not for wgrad_plan's choice: the environment may switch
+// kernels between the query and the call.
+static int64_t wgrad_max_tiles(int64_t batch, int c, int h, int w, int d) {
+  if (batch < 1 || (c != 19 && c != 45) || h < 1 || w < 1 || d < 1 || d > 64 || tc_rows(c, h, w, d) < 1) return 0;
+  int nband = class_bands(h, d, tc_rows(c, h, w, d)).nband;
+  if (c == 19)  // wgrad_plan's other two families, where they take the shape
+    for (const int rows : {tw_rows(c, h, w, d), twd_rows(c, h, w, d)})
+      if (rows > 0) nband = std::max(nband, class_bands(h, d, rows).nband);
+  return batch * nband;
 }
 
 }  // namespace train
 }  // namespace honk
 
 using namespace honk;
+
+// An entry point below is a chain of checks and launches: the first that fails is its status.
+#define HONK_TRY(expr)      \
+  do {                      \
+    const int rc_ = (expr); \
+    if (rc_) return rc_;    \
+  } while (0)
 
 extern "C" int honk_sgd_step_f32(float* params, const float* grads, float* momentum_buf, int64_t n, float lr,
                                  float momentum, float weight_decay, float grad_scale, int32_t nesterov,
@@ -2183,6 +2213,7 @@ extern "C" int honk_sgd_step_f32(float* params, const float* grads, float* momen
   return HONK_OK;
 }
 
+// ---- the block convs: one argument fill, one dispatch of every kernel instance -------------
 namespace {
 int tc_check(const void* a, const void* b, const void* c, int64_t batch, int32_t ch, int32_t h, int32_t w,
              int32_t d) {
@@ -2194,6 +2225,53 @@ int tc_check(const void* a, const void* b, const void* c, int64_t batch, int32_t
     return fail(HONK_ERR_UNSUPPORTED, "conv3x3: width %d at dilation %d too large", w, d);
   if (batch * (int64_t)h > 0x3fffffff) return fail(HONK_ERR_ARG, "conv3x3: batch too large");
   return HONK_OK;
+}
+
+// (the statistics epilogue's aux / part / mask / fm / fi: null here, its entry points set them)
+train::Conv3Args conv_args(const float* x, const float* w, float* y, int64_t batch, int h, int w_, int flip,
+                           const train::ConvPlan& cp) {
+  train::Conv3Args a;
+  a.x = x; a.w = w; a.y = y;
+  a.B = (int)batch; a.H = h; a.W = w_; a.flip = flip ? 1 : 0;
+  a.g = cp.g;
+  a.aux = nullptr; a.part = nullptr; a.mask = nullptr;
+  return a;
+}
+
+template <int MODE, bool FOLD>
+void launch_conv_d(const train::Conv3Args& a, const train::ConvPlan& cp, hipStream_t st) {
+  if (cp.fixed) hipLaunchKernelGGL((train::conv3x3d_kernel<19, MODE, 20, 1, 25, FOLD>), dim3(cp.grid), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((train::conv3x3d_kernel<19, MODE, 0, 0, 0, FOLD>), dim3(cp.grid), dim3(512), 0, st, a);
+}
+// the status of the launch just made (`name`: what a failed one is reported as)
+int launched(const char* name) {
+  HONK_LAUNCH_CHECK(name);
+  return HONK_OK;
+}
+
+// One block conv on the plan's kernel.  mode 0: the plain conv, any family; 1 / 2:
+// conv3x3d_kernel's statistics epilogue (the DMA family), a.fm set: its folded-BatchNorm
+// instance.
+int launch_conv(const train::Conv3Args& a, const train::ConvPlan& cp, int c, int mode, hipStream_t st,
+                const char* name) {
+  const bool fold = a.fm != nullptr;
+  const dim3 grid(cp.grid), blk(256);
+  TimedLaunch tl(st, 2.0 * (double)a.B * a.H * a.W * c * c * 9);
+  if (cp.family == train::FAM_DMA) {
+    if (mode == 0) launch_conv_d<0, false>(a, cp, st);
+    else if (mode == 1 && fold) launch_conv_d<1, true>(a, cp, st);
+    else if (mode == 1) launch_conv_d<1, false>(a, cp, st);
+    else if (fold) launch_conv_d<2, true>(a, cp, st);
+    else launch_conv_d<2, false>(a, cp, st);
+  } else if (cp.family == train::FAM_MFMA) hipLaunchKernelGGL((train::conv3x3m_kernel<19>), grid, blk, 0, st, a);
+  else if (c == 45 && cp.np == 1) hipLaunchKernelGGL((train::conv3x3_kernel<45, 1>), grid, blk, 0, st, a);
+  else if (c == 45) hipLaunchKernelGGL((train::conv3x3_kernel<45, 2>), grid, blk, 0, st, a);
+  else if (cp.np == 1) hipLaunchKernelGGL((train::conv3x3_kernel<19, 1>), grid, blk, 0, st, a);
+  else if (cp.np == 2) hipLaunchKernelGGL((train::conv3x3_kernel<19, 2>), grid, blk, 0, st, a);
+  else if (cp.np == 3) hipLaunchKernelGGL((train::conv3x3_kernel<19, 3>), grid, blk, 0, st, a);
+  else hipLaunchKernelGGL((train::conv3x3_kernel<19, 4>), grid, blk, 0, st, a);
+  tl.done(st);
+  return launched(name);
 }
 }  // namespace
 
@@ -2232,54 +2310,22 @@ extern "C" int honk_conv3x3_plan(int64_t batch, int32_t c, int32_t h, int32_t w_
 
 extern "C" int honk_conv3x3_f32(const float* x, const float* w, float* y, int64_t batch, int32_t c, int32_t h,
                                 int32_t w_, int32_t dil, int32_t flip, void* stream) {
-  int rc = tc_check(x, w, y, batch, c, h, w_, dil);
-  if (rc) return rc;
+  HONK_TRY(tc_check(x, w, y, batch, c, h, w_, dil));
   if (batch == 0) return HONK_OK;
-  train::Conv3Args a;
-  a.x = x; a.w = w; a.y = y;
-  a.B = (int)batch; a.H = h; a.W = w_; a.flip = flip ? 1 : 0;
   const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());
-  a.g = cp.g;
-  const int grid = cp.grid;
-  hipStream_t st = (hipStream_t)stream;
-  TimedLaunch tl(st, 2.0 * (double)batch * h * w_ * c * c * 9);
-  if (cp.family == train::FAM_DMA) {
-    if (cp.fixed) hipLaunchKernelGGL((train::conv3x3d_kernel<19, 0, 20, 1, 25>), dim3(grid), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((train::conv3x3d_kernel<19, 0>), dim3(grid), dim3(512), 0, st, a);
-  } else if (cp.family == train::FAM_MFMA) {
-    hipLaunchKernelGGL((train::conv3x3m_kernel<19>), dim3(grid), dim3(256), 0, st, a);
-  } else if (c == 19) {
-    if (cp.np == 1) hipLaunchKernelGGL((train::conv3x3_kernel<19, 1>), dim3(grid), dim3(256), 0, st, a);
-    else if (cp.np == 2) hipLaunchKernelGGL((train::conv3x3_kernel<19, 2>), dim3(grid), dim3(256), 0, st, a);
-    else if (cp.np == 3) hipLaunchKernelGGL((train::conv3x3_kernel<19, 3>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((train::conv3x3_kernel<19, 4>), dim3(grid), dim3(256), 0, st, a);
-  } else {
-    if (cp.np == 1) hipLaunchKernelGGL((train::conv3x3_kernel<45, 1>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((train::conv3x3_kernel<45, 2>), dim3(grid), dim3(256), 0, st, a);
-  }
-  tl.done(st);
-  HONK_LAUNCH_CHECK("conv3x3_kernel");
-  return HONK_OK;
+  return launch_conv(conv_args(x, w, y, batch, h, w_, flip, cp), cp, c, 0, (hipStream_t)stream, "conv3x3_kernel");
 }
 
 extern "C" size_t honk_conv3x3_wgrad_workspace_bytes(int64_t batch, int32_t c, int32_t h, int32_t w_, int32_t dil) {
-  if (batch < 1 || (c != 19 && c != 45) || h < 1 || w_ < 1 || dil < 1 || dil > 64) return 0;
-  if (train::tc_rows(c, h, w_, dil) < 1) return 0;
-  // the largest grid of any kernel choice (the environment may switch kernels between
-  // this query and the call)
-  int64_t t = batch * train::class_bands(h, dil, train::tc_rows(c, h, w_, dil)).nband;
-  const int tw = c == 19 ? train::tw_rows(c, h, w_, dil) : 0;
-  if (tw > 0) t = std::max<int64_t>(t, batch * train::class_bands(h, dil, tw).nband);
-  const int td = c == 19 ? train::twd_rows(c, h, w_, dil) : 0;  // grid <= CUs < tc_grid's 2 CUs
-  if (td > 0) t = std::max<int64_t>(t, batch * train::class_bands(h, dil, td).nband);
-  return (size_t)train::tc_grid(t, cu_count()) * c * c * 9 * sizeof(float);
+  const int64_t tiles = train::wgrad_max_tiles(batch, c, h, w_, dil);
+  // (a DMA family's grid, at most one workgroup per CU, is within tc_grid's two)
+  return tiles ? (size_t)train::tc_grid(tiles, cu_count()) * c * c * 9 * sizeof(float) : 0;
 }
 
 namespace {
 int conv3x3_wgrad(const float* x, const float* dy, float* dw, int64_t batch, int32_t c, int32_t h, int32_t w_,
                   int32_t dil, const float* fm, const float* fi, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = tc_check(x, dy, dw, batch, c, h, w_, dil);
-  if (rc) return rc;
+  HONK_TRY(tc_check(x, dy, dw, batch, c, h, w_, dil));
   hipStream_t st = (hipStream_t)stream;
   const int n = c * c * 9;
   if (batch == 0) {
@@ -2313,8 +2359,7 @@ int conv3x3_wgrad(const float* x, const float* dy, float* dw, int64_t batch, int
   HONK_LAUNCH_CHECK("wgrad3x3_kernel");
   hipLaunchKernelGGL(train::wsum_kernel, dim3((unsigned)cdiv(n, train::WSUM_OUT)), dim3(256), 0, st, (const float*)workspace, dw,
                      n, grid);
-  HONK_LAUNCH_CHECK("wsum_kernel");
-  return HONK_OK;
+  return launched("wsum_kernel");
 }
 }  // namespace
 
@@ -2331,12 +2376,107 @@ extern "C" int honk_conv3x3_wgrad_bn_f32(const float* x, const float* dy, float*
   return conv3x3_wgrad(x, dy, dw, batch, c, h, w_, dil, fold_mean, fold_invstd, workspace, ws_bytes, stream);
 }
 
+// ---- train-mode BatchNorm and the res tail: one chain ---------------------------------------
+//   (sum the partials ->) finish the statistics -> one elementwise kernel
+// Every entry point below is written in BnChain's words: its pointer checks, the call's dims,
+// where the partial sums lie (own / conv), then one launcher per kernel of the chain.
+namespace {
 // SyncBN (honk_amd/syncbn.py): the ranks' statistics partials are all-reduced before a
 // BatchNorm finalises them, and the element count is the whole job's -- this rank's times
 // the scale (the ranks' equal batches; thread-local, 1 outside a synchronised training)
-namespace {
 thread_local double g_bn_nscale = 1.0;
-double bn_count(int64_t batch, int64_t hw) { return (double)batch * (double)hw * g_bn_nscale; }
+
+// a statistics buffer: [c][S][2] doubles of partial sums, then 4 c floats
+size_t partials_bytes(int c, int S) { return (size_t)c * S * 2 * sizeof(double); }
+size_t stats_buffer_bytes(int c, int S) { return partials_bytes(c, S) + (size_t)4 * c * sizeof(float); }
+
+struct Partials {
+  double* part;  // [c][S][2]
+  int S;
+  float* m;  // the 2 c floats behind them (bn_bstats_kernel's two means)
+};
+
+struct BnChain {
+  int64_t batch;
+  int c;
+  int64_t hw;
+  int hh, ww;  // of a call that names its map (the conv epilogues' statistics), else 0
+  hipStream_t st;
+  Partials p{nullptr, 0, nullptr};
+
+  BnChain(int64_t b, int c_, int64_t hw_, void* stream) : batch(b), c(c_), hw(hw_), hh(0), ww(0), st((hipStream_t)stream) {}
+  BnChain(int64_t b, int c_, int h, int w, void* stream)
+      : batch(b), c(c_), hw(h < 1 || w < 1 ? 0 : (int64_t)h * w), hh(h), ww(w), st((hipStream_t)stream) {}
+  int check(const char* what) const {
+    if (batch < 1 || c < 1 || hw < 1 || hw > 0x7fffffff || batch > 0x7fffffff) return fail(HONK_ERR_ARG, "%s", what);
+    return HONK_OK;
+  }
+  int64_t total() const { return batch * c * hw; }
+  double count() const { return (double)batch * (double)hw * g_bn_nscale; }
+  // the elementwise kernels: one thread per float4 where the rows allow, else per element
+  dim3 grid() const { return dim3((unsigned)cdiv((hw & 3) == 0 ? total() / 4 : total(), 256)); }
+
+  // Where the partials lie, one of three ways.  This call's own workspace, summed here (sum /
+  // sum_tail), or the caller's pre-summed buffer of the same layout (honk_bn_partials_f32;
+  // SyncBN: all-reduced): bn_slices partials a channel ...
+  int at(void* buf, int S) {
+    p = {(double*)buf, S, (float*)((double*)buf + (size_t)c * S * 2)};
+    return HONK_OK;
+  }
+  int own(void* buf, size_t bytes) {
+    const int S = train::bn_slices((int)batch, c);
+    const size_t need = stats_buffer_bytes(c, S);
+    if (!buf || bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", bytes, need);
+    return at(buf, S);
+  }
+  // ... or the buffer a conv's statistics epilogue summed into (conv_epilogue): one partial per
+  // workgroup of its grid (bytes: where the entry point is told the size)
+  int conv(int dil, const void* buf, size_t bytes = SIZE_MAX) {
+    const int S = train::stats_grid(batch, c, hh, ww, dil);
+    if (S <= 0) return fail(HONK_ERR_UNSUPPORTED, "res tail: no statistics epilogue for this shape");
+    const size_t need = stats_buffer_bytes(c, S);
+    if (bytes < need) return fail(HONK_ERR_WORKSPACE, "statistics buffer %zu B < required %zu B", bytes, need);
+    return at(const_cast<void*>(buf), S);
+  }
+
+  // (sum a, sum a*b) per channel and slice (b null: a*a); sum_tail: of s = relu(h) [+ old]
+  int sum(const float* a, const float* b) const {
+    hipLaunchKernelGGL(train::bn_partial_kernel, dim3(c, p.S), dim3(256), 0, st, a, b, p.part, (int)batch, c, (int)hw, p.S);
+    return launched("bn_partial_kernel");
+  }
+  int sum_tail(const float* h, const float* old) const {
+    hipLaunchKernelGGL(train::tail_partial_kernel, dim3(c, p.S), dim3(256), 0, st, h, old, p.part, (int)batch, c, (int)hw, p.S);
+    return launched("tail_partial_kernel");
+  }
+  int finish_fwd(float* mean, float* invstd, float* running_mean, float* running_var, float momentum, float eps) const {
+    hipLaunchKernelGGL(train::bn_stats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)p.part, mean,
+                       invstd, running_mean, running_var, c, p.S, count(), momentum, eps);
+    return launched("bn_stats_kernel");
+  }
+  int finish_bwd() const {  // mean(dy) into p.m, mean(dy * y) into p.m + c
+    hipLaunchKernelGGL(train::bn_bstats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)p.part, p.m,
+                       p.m + c, c, p.S, count());
+    return launched("bn_bstats_kernel");
+  }
+  int apply(const float* a, const float* b, const float* u, const float* v, const float* w, float* out) const {
+    hipLaunchKernelGGL(train::bn_apply_kernel, grid(), dim3(256), 0, st, a, b, u, v, w, out, total(), c, (int)hw);
+    return launched("bn_apply_kernel");
+  }
+  template <bool S_IN>
+  int tail_fwd(const float* h, const float* old, const float* mean, const float* invstd, float* y, float* s) const {
+    hipLaunchKernelGGL(train::tail_fwd_kernel<S_IN>, grid(), dim3(256), 0, st, h, old, mean, invstd, y, s, total(), c,
+                       (int)hw);
+    return launched("tail_fwd_kernel");
+  }
+  // hm: h, or (MASK) the conv epilogue's mask words; ym (FOLD): the folded BatchNorm's mean
+  template <bool MASK, bool FOLD = false>
+  int tail_bwd(const float* gy, const float* y, const float* gs, const void* hm, const float* invstd, float* gh,
+               float* gold, const float* ym = nullptr) const {
+    hipLaunchKernelGGL((train::tail_bwd_kernel<MASK, FOLD>), grid(), dim3(256), 0, st, gy, y, gs, hm,
+                       (const float*)p.m, invstd, (const float*)(p.m + c), gh, gold, total(), c, (int)hw, ym);
+    return launched("tail_bwd_kernel");
+  }
+};
 }  // namespace
 
 extern "C" int honk_bn_count_scale(double k) {
@@ -2352,146 +2492,86 @@ extern "C" int honk_bn_count_scale(double k) {
 extern "C" int honk_bn_partials_f32(const float* a, const float* b, void* part, size_t part_bytes, int64_t batch,
                                     int32_t c, int64_t hw, void* stream) {
   if (!a || !part) return fail(HONK_ERR_ARG, "null pointer argument");
-  if (batch < 1 || c < 1 || hw < 1 || hw > 0x7fffffff || batch > 0x7fffffff) return fail(HONK_ERR_ARG, "bad batchnorm shape");
+  BnChain ch(batch, c, hw, stream);
+  HONK_TRY(ch.check("bad batchnorm shape"));
   const int S = train::bn_slices((int)batch, c);
-  if (part_bytes < (size_t)c * S * 2 * sizeof(double)) return fail(HONK_ERR_WORKSPACE, "partials buffer too small");
-  hipLaunchKernelGGL(train::bn_partial_kernel, dim3(c, S), dim3(256), 0, (hipStream_t)stream, a, b, (double*)part,
-                     (int)batch, c, (int)hw, S);
-  HONK_LAUNCH_CHECK("bn_partial_kernel");
-  return HONK_OK;
+  if (part_bytes < partials_bytes(c, S)) return fail(HONK_ERR_WORKSPACE, "partials buffer too small");
+  ch.at(part, S);
+  return ch.sum(a, b);
 }
 
 extern "C" size_t honk_bn_train_workspace_bytes(int64_t batch, int32_t c, int64_t hw) {
   if (batch < 1 || c < 1 || hw < 1) return 0;
-  return (size_t)c * train::bn_slices((int)batch, c) * 2 * sizeof(double) + (size_t)4 * c * sizeof(float);
+  return stats_buffer_bytes(c, train::bn_slices((int)batch, c));
 }
 
 extern "C" int honk_bn_train_fwd_f32(const float* x, float* y, float* mean, float* invstd, float* running_mean,
                                      float* running_var, int64_t batch, int32_t c, int64_t hw, float momentum,
                                      float eps, void* workspace, size_t ws_bytes, void* stream) {
   if (!x || !y || !mean || !invstd || (!running_mean != !running_var)) return fail(HONK_ERR_ARG, "null pointer argument");
-  if (batch < 1 || c < 1 || hw < 1 || hw > 0x7fffffff || batch > 0x7fffffff) return fail(HONK_ERR_ARG, "bad batchnorm shape");
-  const size_t need = honk_bn_train_workspace_bytes(batch, c, hw);
-  if (!workspace || ws_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
-  const int S = train::bn_slices((int)batch, c);
-  double* part = (double*)workspace;
-  hipLaunchKernelGGL(train::bn_partial_kernel, dim3(c, S), dim3(256), 0, st, x, (const float*)nullptr, part,
-                     (int)batch, c, (int)hw, S);
-  HONK_LAUNCH_CHECK("bn_partial_kernel");
-  hipLaunchKernelGGL(train::bn_stats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)part, mean,
-                     invstd, running_mean, running_var, c, S, bn_count(batch, hw), momentum, eps);
-  HONK_LAUNCH_CHECK("bn_stats_kernel");
-  const int64_t total = batch * c * hw;
-  const int64_t nthr = (hw & 3) == 0 ? total / 4 : total;
-  hipLaunchKernelGGL(train::bn_apply_kernel, dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, x,
-                     (const float*)nullptr, (const float*)mean, (const float*)invstd, (const float*)nullptr, y, total,
-                     c, (int)hw);
-  HONK_LAUNCH_CHECK("bn_apply_kernel");
-  return HONK_OK;
+  BnChain ch(batch, c, hw, stream);
+  HONK_TRY(ch.check("bad batchnorm shape"));
+  HONK_TRY(ch.own(workspace, ws_bytes));
+  HONK_TRY(ch.sum(x, nullptr));
+  HONK_TRY(ch.finish_fwd(mean, invstd, running_mean, running_var, momentum, eps));
+  return ch.apply(x, nullptr, mean, invstd, nullptr, y);
 }
 
 extern "C" int honk_bn_train_bwd_f32(const float* dy, const float* y, const float* invstd, float* dx, int64_t batch,
                                      int32_t c, int64_t hw, void* workspace, size_t ws_bytes, void* stream) {
   if (!dy || !y || !invstd || !dx) return fail(HONK_ERR_ARG, "null pointer argument");
-  if (batch < 1 || c < 1 || hw < 1 || hw > 0x7fffffff || batch > 0x7fffffff) return fail(HONK_ERR_ARG, "bad batchnorm shape");
-  const size_t need = honk_bn_train_workspace_bytes(batch, c, hw);
-  if (!workspace || ws_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
-  const int S = train::bn_slices((int)batch, c);
-  double* part = (double*)workspace;
-  float* m = (float*)(part + (size_t)c * S * 2);
-  hipLaunchKernelGGL(train::bn_partial_kernel, dim3(c, S), dim3(256), 0, st, dy, y, part, (int)batch, c, (int)hw, S);
-  HONK_LAUNCH_CHECK("bn_partial_kernel");
-  hipLaunchKernelGGL(train::bn_bstats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)part, m,
-                     m + c, c, S, bn_count(batch, hw));
-  HONK_LAUNCH_CHECK("bn_bstats_kernel");
-  const int64_t total = batch * c * hw;
-  const int64_t nthr = (hw & 3) == 0 ? total / 4 : total;
-  hipLaunchKernelGGL(train::bn_apply_kernel, dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, dy, y,
-                     (const float*)m, invstd, (const float*)(m + c), dx, total, c, (int)hw);
-  HONK_LAUNCH_CHECK("bn_apply_kernel");
-  return HONK_OK;
+  BnChain ch(batch, c, hw, stream);
+  HONK_TRY(ch.check("bad batchnorm shape"));
+  HONK_TRY(ch.own(workspace, ws_bytes));
+  HONK_TRY(ch.sum(dy, y));
+  HONK_TRY(ch.finish_bwd());
+  return ch.apply(dy, y, ch.p.m, invstd, ch.p.m + c, dx);
 }
 
 extern "C" int honk_res_tail_fwd_f32(const float* h, const float* old, float* s, float* y, float* mean, float* invstd,
                                      float* running_mean, float* running_var, int64_t batch, int32_t c, int64_t hw,
                                      float momentum, float eps, void* workspace, size_t ws_bytes, void* stream) {
   if (!h || !y || !mean || !invstd || (!running_mean != !running_var)) return fail(HONK_ERR_ARG, "null pointer argument");
-  if (batch < 1 || c < 1 || hw < 1 || hw > 0x7fffffff || batch > 0x7fffffff) return fail(HONK_ERR_ARG, "bad batchnorm shape");
-  const size_t need = honk_bn_train_workspace_bytes(batch, c, hw);
-  if (!workspace || ws_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
-  const int S = train::bn_slices((int)batch, c);
-  double* part = (double*)workspace;
-  hipLaunchKernelGGL(train::tail_partial_kernel, dim3(c, S), dim3(256), 0, st, h, old, part, (int)batch, c, (int)hw, S);
-  HONK_LAUNCH_CHECK("tail_partial_kernel");
-  hipLaunchKernelGGL(train::bn_stats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)part, mean,
-                     invstd, running_mean, running_var, c, S, bn_count(batch, hw), momentum, eps);
-  HONK_LAUNCH_CHECK("bn_stats_kernel");
-  const int64_t total = batch * c * hw;
-  const int64_t nthr = (hw & 3) == 0 ? total / 4 : total;
-  hipLaunchKernelGGL(train::tail_fwd_kernel<false>, dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, h, old,
-                     (const float*)mean, (const float*)invstd, y, s, total, c, (int)hw);
-  HONK_LAUNCH_CHECK("tail_fwd_kernel");
-  return HONK_OK;
+  BnChain ch(batch, c, hw, stream);
+  HONK_TRY(ch.check("bad batchnorm shape"));
+  HONK_TRY(ch.own(workspace, ws_bytes));
+  HONK_TRY(ch.sum_tail(h, old));
+  HONK_TRY(ch.finish_fwd(mean, invstd, running_mean, running_var, momentum, eps));
+  return ch.tail_fwd<false>(h, old, mean, invstd, y, s);
 }
 
 extern "C" int honk_res_tail_bwd_f32(const float* gy, const float* gs, const float* y, const float* invstd,
                                      const float* h, float* gh, float* gold, int64_t batch, int32_t c, int64_t hw,
                                      void* workspace, size_t ws_bytes, void* stream) {
   if (!gy || !y || !invstd || !h || !gh) return fail(HONK_ERR_ARG, "null pointer argument");
-  if (batch < 1 || c < 1 || hw < 1 || hw > 0x7fffffff || batch > 0x7fffffff) return fail(HONK_ERR_ARG, "bad batchnorm shape");
-  const size_t need = honk_bn_train_workspace_bytes(batch, c, hw);
-  if (!workspace || ws_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
-  const int S = train::bn_slices((int)batch, c);
-  double* part = (double*)workspace;
-  float* m = (float*)(part + (size_t)c * S * 2);
-  hipLaunchKernelGGL(train::bn_partial_kernel, dim3(c, S), dim3(256), 0, st, gy, y, part, (int)batch, c, (int)hw, S);
-  HONK_LAUNCH_CHECK("bn_partial_kernel");
-  hipLaunchKernelGGL(train::bn_bstats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)part, m,
-                     m + c, c, S, bn_count(batch, hw));
-  HONK_LAUNCH_CHECK("bn_bstats_kernel");
-  const int64_t total = batch * c * hw;
-  const int64_t nthr = (hw & 3) == 0 ? total / 4 : total;
-  hipLaunchKernelGGL(train::tail_bwd_kernel<false>, dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, gy, y, gs, h,
-                     (const float*)m, invstd, (const float*)(m + c), gh, gold, total, c, (int)hw,
-                     (const float*)nullptr);
-  HONK_LAUNCH_CHECK("tail_bwd_kernel");
-  return HONK_OK;
+  BnChain ch(batch, c, hw, stream);
+  HONK_TRY(ch.check("bad batchnorm shape"));
+  HONK_TRY(ch.own(workspace, ws_bytes));
+  HONK_TRY(ch.sum(gy, y));
+  HONK_TRY(ch.finish_bwd());
+  return ch.tail_bwd<false>(gy, y, gs, h, invstd, gh, gold);
 }
 
-// ---- the statistics epilogue (conv3x3d_kernel MODE 1 / 2) and the tails that take
-// its partial sums instead of their own pass over the tensors ----
+// ---- the statistics epilogue (conv3x3d_kernel MODE 1 / 2) and the tails that take its
+// partial sums (BnChain::conv) instead of their own pass over the tensors ----
 namespace {
-int stats_grid(int64_t batch, int c, int h, int w_, int dil) {
-  if (batch < 1 || c != 19 || !train::plan_shape_ok(c, h, w_, dil)) return 0;
-  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());
-  return cp.family == train::FAM_DMA ? cp.grid : 0;
-}
-}  // namespace
-
-namespace {
-// conv3x3d_kernel with the statistics epilogue: mode 1 / 2, the fixed-geometry instance
-// where it applies, the folded-BatchNorm instance when a.fm is set
-void launch_conv_stats(const train::Conv3Args& a, int mode, const train::ConvPlan& cp, hipStream_t st) {
-  const bool fx = cp.fixed, fo = a.fm != nullptr;
-  const int S = cp.grid;
-#define HONK_CS(M, FO)                                                                                           \
-  if (fx) hipLaunchKernelGGL((train::conv3x3d_kernel<19, M, 20, 1, 25, FO>), dim3(S), dim3(512), 0, st, a); \
-  else hipLaunchKernelGGL((train::conv3x3d_kernel<19, M, 0, 0, 0, FO>), dim3(S), dim3(512), 0, st, a);
-  if (mode == 1 && fo) { HONK_CS(1, true) }
-  else if (mode == 1) { HONK_CS(1, false) }
-  else if (fo) { HONK_CS(2, true) }
-  else { HONK_CS(2, false) }
-#undef HONK_CS
+// After the entry point's own checks and argument fill.  `what` ("statistics" / "tail") names
+// the epilogue in a refusal, `name` the launch.
+int conv_epilogue(train::Conv3Args a, const train::ConvPlan& cp, int c, int mode, void* stats, size_t stats_bytes,
+                  void* stream, const char* what, const char* name) {
+  const int S = c == 19 ? train::plan_stats(cp) : 0;  // (no clip: an empty grid)
+  if (S <= 0) return fail(HONK_ERR_UNSUPPORTED, "conv3x3 %s epilogue: shape outside conv3x3d_kernel", what);
+  const size_t need = stats_buffer_bytes(c, S);
+  if (!stats || stats_bytes < need)
+    return fail(HONK_ERR_WORKSPACE, "statistics buffer %zu B < required %zu B", stats_bytes, need);
+  a.part = (double*)stats;
+  return launch_conv(a, cp, c, mode, (hipStream_t)stream, name);
 }
 }  // namespace
 
 extern "C" size_t honk_conv3x3_stats_bytes(int64_t batch, int32_t c, int32_t h, int32_t w_, int32_t dil) {
-  const int S = stats_grid(batch, c, h, w_, dil);
-  return S > 0 ? (size_t)c * S * 2 * sizeof(double) + (size_t)4 * c * sizeof(float) : 0;
+  const int S = train::stats_grid(batch, c, h, w_, dil);
+  return S > 0 ? stats_buffer_bytes(c, S) : 0;
 }
 
 extern "C" int honk_conv3x3_stats_bn_f32(const float* x, const float* w, float* y, int64_t batch, int32_t c,
@@ -2499,30 +2579,13 @@ extern "C" int honk_conv3x3_stats_bn_f32(const float* x, const float* w, float* 
                                          const float* aux, const float* fold_mean, const float* fold_invstd,
                                          void* stats, size_t stats_bytes, void* stream) {
   if (!fold_mean != !fold_invstd) return fail(HONK_ERR_ARG, "null pointer argument");
-  int rc = tc_check(x, w, y, batch, c, h, w_, dil);
-  if (rc) return rc;
+  HONK_TRY(tc_check(x, w, y, batch, c, h, w_, dil));
   if (mode != 1 && mode != 2) return fail(HONK_ERR_ARG, "conv3x3 statistics mode %d (1 or 2)", mode);
   if (mode == 2 && !aux) return fail(HONK_ERR_ARG, "conv3x3 statistics mode 2 needs the BN output");
-  const int S = stats_grid(batch, c, h, w_, dil);
-  if (S <= 0) return fail(HONK_ERR_UNSUPPORTED, "conv3x3 statistics epilogue: shape outside conv3x3d_kernel");
-  if (!stats || stats_bytes < honk_conv3x3_stats_bytes(batch, c, h, w_, dil))
-    return fail(HONK_ERR_WORKSPACE, "statistics buffer %zu B < required %zu B", stats_bytes,
-                honk_conv3x3_stats_bytes(batch, c, h, w_, dil));
-  train::Conv3Args a;
-  a.x = x; a.w = w; a.y = y;
-  a.B = (int)batch; a.H = h; a.W = w_; a.flip = flip ? 1 : 0;
-  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());  // (S > 0: the DMA family)
-  a.g = cp.g;
-  a.aux = aux;
-  a.part = (double*)stats;
-  a.mask = nullptr;
-  a.fm = fold_mean; a.fi = fold_invstd;
-  hipStream_t st = (hipStream_t)stream;
-  TimedLaunch tl(st, 2.0 * (double)batch * h * w_ * c * c * 9);
-  launch_conv_stats(a, mode, cp, st);
-  tl.done(st);
-  HONK_LAUNCH_CHECK("conv3x3d_kernel");
-  return HONK_OK;
+  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());
+  train::Conv3Args a = conv_args(x, w, y, batch, h, w_, flip, cp);
+  a.aux = aux; a.fm = fold_mean; a.fi = fold_invstd;
+  return conv_epilogue(a, cp, c, mode, stats, stats_bytes, stream, "statistics", "conv3x3d_kernel");
 }
 
 extern "C" int honk_conv3x3_stats_f32(const float* x, const float* w, float* y, int64_t batch, int32_t c, int32_t h,
@@ -2537,29 +2600,12 @@ extern "C" int honk_conv3x3_tail_bn_f32(const float* x, const float* w, float* s
                                         const float* fold_mean, const float* fold_invstd, void* stats,
                                         size_t stats_bytes, void* stream) {
   if (!fold_mean != !fold_invstd) return fail(HONK_ERR_ARG, "null pointer argument");
-  int rc = tc_check(x, w, s, batch, c, h, w_, dil);
-  if (rc) return rc;
+  HONK_TRY(tc_check(x, w, s, batch, c, h, w_, dil));
   if (!mask) return fail(HONK_ERR_ARG, "null pointer argument");
-  const int S = stats_grid(batch, c, h, w_, dil);
-  if (S <= 0) return fail(HONK_ERR_UNSUPPORTED, "conv3x3 tail epilogue: shape outside conv3x3d_kernel");
-  if (!stats || stats_bytes < honk_conv3x3_stats_bytes(batch, c, h, w_, dil))
-    return fail(HONK_ERR_WORKSPACE, "statistics buffer %zu B < required %zu B", stats_bytes,
-                honk_conv3x3_stats_bytes(batch, c, h, w_, dil));
-  train::Conv3Args a;
-  a.x = x; a.w = w; a.y = s;
-  a.B = (int)batch; a.H = h; a.W = w_; a.flip = 0;
-  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());  // (S > 0: the DMA family)
-  a.g = cp.g;
-  a.aux = old;
-  a.part = (double*)stats;
-  a.mask = mask;
-  a.fm = fold_mean; a.fi = fold_invstd;
-  hipStream_t st = (hipStream_t)stream;
-  TimedLaunch tl(st, 2.0 * (double)batch * h * w_ * c * c * 9);
-  launch_conv_stats(a, 1, cp, st);
-  tl.done(st);
-  HONK_LAUNCH_CHECK("conv3x3d_kernel (tail epilogue)");
-  return HONK_OK;
+  const train::ConvPlan cp = train::conv_plan(batch, c, h, w_, dil, cu_count());
+  train::Conv3Args a = conv_args(x, w, s, batch, h, w_, 0, cp);
+  a.aux = old; a.mask = mask; a.fm = fold_mean; a.fi = fold_invstd;
+  return conv_epilogue(a, cp, c, 1, stats, stats_bytes, stream, "tail", "conv3x3d_kernel (tail epilogue)");
 }
 
 extern "C" int honk_conv3x3_tail_f32(const float* x, const float* w, float* s, uint32_t* mask, int64_t batch,
@@ -2570,8 +2616,7 @@ extern "C" int honk_conv3x3_tail_f32(const float* x, const float* w, float* s, u
 }
 
 extern "C" int honk_conv3x3_bn_fold_check(int64_t batch, int32_t c, int32_t h, int32_t w_, int32_t dil) {
-  if (stats_grid(batch, c, h, w_, dil) <= 0 || !train::plan(batch, c, h, w_, dil, cu_count()).fold)
-    return fail(HONK_ERR_UNSUPPORTED, "conv3x3: no folded BatchNorm for this shape");
+  if (!train::fold_ok(batch, c, h, w_, dil)) return fail(HONK_ERR_UNSUPPORTED, "conv3x3: no folded BatchNorm for this shape");
   return HONK_OK;
 }
 
@@ -2580,69 +2625,29 @@ extern "C" int honk_res_tail_fwd_s_f32(const float* s, float* y, float* mean, fl
                                        int32_t ww, int32_t dil, float momentum, float eps, void* stream) {
   if (!s || !mean || !invstd || !stats || (!running_mean != !running_var))
     return fail(HONK_ERR_ARG, "null pointer argument");
-  const int S = stats_grid(batch, c, hh, ww, dil);
-  if (S <= 0) return fail(HONK_ERR_UNSUPPORTED, "res tail: no statistics epilogue for this shape");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t hw = (int64_t)hh * ww;
-  hipLaunchKernelGGL(train::bn_stats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)stats,
-                     mean, invstd, running_mean, running_var, c, S, bn_count(batch, hw), momentum, eps);
-  HONK_LAUNCH_CHECK("bn_stats_kernel");
+  BnChain ch(batch, c, hh, ww, stream);
+  HONK_TRY(ch.conv(dil, stats));
+  HONK_TRY(ch.finish_fwd(mean, invstd, running_mean, running_var, momentum, eps));
   if (!y) return HONK_OK;  // the next conv folds the BatchNorm in (honk_conv3x3_tail_bn_f32)
-  const int64_t total = batch * c * hw;
-  const int64_t nthr = (hw & 3) == 0 ? total / 4 : total;
-  hipLaunchKernelGGL(train::tail_fwd_kernel<true>, dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, s,
-                     (const float*)nullptr, (const float*)mean, (const float*)invstd, y, (float*)nullptr, total, c,
-                     (int)hw);
-  HONK_LAUNCH_CHECK("tail_fwd_kernel");
-  return HONK_OK;
+  return ch.tail_fwd<true>(s, nullptr, mean, invstd, y, nullptr);
 }
 
 namespace {
+// dil > 0: the input-gradient conv's epilogue summed the partials (its grid's); < 0: the
+// caller did (honk_bn_partials_f32; SyncBN: all-reduced); 0: no conv consumed the gradient (the
+// last block), they are summed here.  ym: the folded BatchNorm's mean (y then holds the tail's s)
 int res_tail_bwd_mask(const float* gy, const float* gs, const float* y, const float* ym, const float* invstd,
                       const uint32_t* mask, float* gh, float* gold, int64_t batch, int32_t c, int32_t hh, int32_t ww,
                       int32_t dil, void* stats, size_t stats_bytes, void* stream) {
   if (!gy || !y || !invstd || !mask || !gh || !stats) return fail(HONK_ERR_ARG, "null pointer argument");
   if (ym && dil == 0) return fail(HONK_ERR_UNSUPPORTED, "res tail: a folded BatchNorm needs the conv's statistics");
-  if (batch < 1 || c < 1 || hh < 1 || ww < 1 || batch > 0x7fffffff || (int64_t)hh * ww > 0x7fffffff)
-    return fail(HONK_ERR_ARG, "bad res tail shape");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t hw = (int64_t)hh * ww;
-  double* part = (double*)stats;
-  int S;
-  if (dil > 0) {  // the input-gradient conv's epilogue summed them (its grid's partials)
-    S = stats_grid(batch, c, hh, ww, dil);
-    if (S <= 0) return fail(HONK_ERR_UNSUPPORTED, "res tail: no statistics epilogue for this shape");
-    if (stats_bytes < honk_conv3x3_stats_bytes(batch, c, hh, ww, dil))
-      return fail(HONK_ERR_WORKSPACE, "statistics buffer %zu B < required %zu B", stats_bytes,
-                  honk_conv3x3_stats_bytes(batch, c, hh, ww, dil));
-  } else if (dil < 0) {  // the caller's partials (honk_bn_partials_f32; SyncBN: all-reduced)
-    const size_t need = honk_bn_train_workspace_bytes(batch, c, hw);
-    if (stats_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", stats_bytes, need);
-    S = train::bn_slices((int)batch, c);
-  } else {  // dil = 0: no conv consumed the gradient (the last block): sum them here
-    const size_t need = honk_bn_train_workspace_bytes(batch, c, hw);
-    if (stats_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", stats_bytes, need);
-    S = train::bn_slices((int)batch, c);
-    hipLaunchKernelGGL(train::bn_partial_kernel, dim3(c, S), dim3(256), 0, st, gy, y, part, (int)batch, c, (int)hw,
-                       S);
-    HONK_LAUNCH_CHECK("bn_partial_kernel");
-  }
-  float* m = (float*)(part + (size_t)c * S * 2);
-  hipLaunchKernelGGL(train::bn_bstats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)part, m,
-                     m + c, c, S, bn_count(batch, hw));
-  HONK_LAUNCH_CHECK("bn_bstats_kernel");
-  const int64_t total = batch * c * hw;
-  const int64_t nthr = (hw & 3) == 0 ? total / 4 : total;
-  if (ym)
-    hipLaunchKernelGGL((train::tail_bwd_kernel<true, true>), dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, gy, y,
-                       gs, (const void*)mask, (const float*)m, invstd, (const float*)(m + c), gh, gold, total, c,
-                       (int)hw, ym);
-  else
-    hipLaunchKernelGGL((train::tail_bwd_kernel<true>), dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, gy, y, gs,
-                       (const void*)mask, (const float*)m, invstd, (const float*)(m + c), gh, gold, total, c, (int)hw,
-                       (const float*)nullptr);
-  HONK_LAUNCH_CHECK("tail_bwd_kernel");
-  return HONK_OK;
+  BnChain ch(batch, c, hh, ww, stream);
+  HONK_TRY(ch.check("bad res tail shape"));
+  HONK_TRY(dil > 0 ? ch.conv(dil, stats, stats_bytes) : ch.own(stats, stats_bytes));
+  if (dil == 0) HONK_TRY(ch.sum(gy, y));
+  HONK_TRY(ch.finish_bwd());
+  if (ym) return ch.tail_bwd<true, true>(gy, y, gs, mask, invstd, gh, gold, ym);
+  return ch.tail_bwd<true>(gy, y, gs, mask, invstd, gh, gold);
 }
 }  // namespace
 
@@ -2669,41 +2674,20 @@ extern "C" int honk_res_tail_fwd_part_f32(const float* h, const float* old, floa
                                           int32_t dil, float momentum, float eps, void* stream) {
   if (!h || !y || !mean || !invstd || !stats || (!running_mean != !running_var))
     return fail(HONK_ERR_ARG, "null pointer argument");
-  const int S = stats_grid(batch, c, hh, ww, dil);
-  if (S <= 0) return fail(HONK_ERR_UNSUPPORTED, "res tail: no statistics epilogue for this shape");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t hw = (int64_t)hh * ww;
-  hipLaunchKernelGGL(train::bn_stats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)stats,
-                     mean, invstd, running_mean, running_var, c, S, bn_count(batch, hw), momentum, eps);
-  HONK_LAUNCH_CHECK("bn_stats_kernel");
-  const int64_t total = batch * c * hw;
-  const int64_t nthr = (hw & 3) == 0 ? total / 4 : total;
-  hipLaunchKernelGGL(train::tail_fwd_kernel<false>, dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, h, old,
-                     (const float*)mean, (const float*)invstd, y, s, total, c, (int)hw);
-  HONK_LAUNCH_CHECK("tail_fwd_kernel");
-  return HONK_OK;
+  BnChain ch(batch, c, hh, ww, stream);
+  HONK_TRY(ch.conv(dil, stats));
+  HONK_TRY(ch.finish_fwd(mean, invstd, running_mean, running_var, momentum, eps));
+  return ch.tail_fwd<false>(h, old, mean, invstd, y, s);
 }
 
 extern "C" int honk_res_tail_bwd_part_f32(const float* gy, const float* gs, const float* y, const float* invstd,
                                           const float* h, float* gh, float* gold, void* stats, int64_t batch,
                                           int32_t c, int32_t hh, int32_t ww, int32_t dil, void* stream) {
   if (!gy || !y || !invstd || !h || !gh || !stats) return fail(HONK_ERR_ARG, "null pointer argument");
-  const int S = stats_grid(batch, c, hh, ww, dil);
-  if (S <= 0) return fail(HONK_ERR_UNSUPPORTED, "res tail: no statistics epilogue for this shape");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t hw = (int64_t)hh * ww;
-  double* part = (double*)stats;
-  float* m = (float*)(part + (size_t)c * S * 2);
-  hipLaunchKernelGGL(train::bn_bstats_kernel, dim3((unsigned)c), dim3(256), 0, st, (const double*)part, m,
-                     m + c, c, S, bn_count(batch, hw));
-  HONK_LAUNCH_CHECK("bn_bstats_kernel");
-  const int64_t total = batch * c * hw;
-  const int64_t nthr = (hw & 3) == 0 ? total / 4 : total;
-  hipLaunchKernelGGL(train::tail_bwd_kernel<false>, dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, st, gy, y, gs, h,
-                     (const float*)m, invstd, (const float*)(m + c), gh, gold, total, c, (int)hw,
-                     (const float*)nullptr);
-  HONK_LAUNCH_CHECK("tail_bwd_kernel");
-  return HONK_OK;
+  BnChain ch(batch, c, hh, ww, stream);
+  HONK_TRY(ch.conv(dil, stats));
+  HONK_TRY(ch.finish_bwd());
+  return ch.tail_bwd<false>(gy, y, gs, h, invstd, gh, gold);
 }
 
 namespace {
@@ -2722,13 +2706,11 @@ int stem_grid(int64_t batch) { return (int)std::min<int64_t>(batch, 3 * (int64_t
 
 extern "C" int honk_res_stem_fwd_f32(const float* x, const float* w0, float* y, int64_t batch, int32_t c, int32_t h,
                                      int32_t w_, int32_t ph, int32_t pw, void* stream) {
-  int rc = stem_check(x, w0, y, batch, c, h, w_, ph, pw);
-  if (rc) return rc;
+  HONK_TRY(stem_check(x, w0, y, batch, c, h, w_, ph, pw));
   if (batch == 0) return HONK_OK;
   train::StemArgs a{x, w0, nullptr, y, nullptr, (int)batch, c, h, w_, ph, pw};
   train::stem_launch<false>(a, stem_grid(batch), (hipStream_t)stream);
-  HONK_LAUNCH_CHECK("stem_kernel");
-  return HONK_OK;
+  return launched("stem_kernel");
 }
 
 extern "C" size_t honk_res_stem_wgrad_workspace_bytes(int64_t batch, int32_t c) {
@@ -2739,8 +2721,7 @@ extern "C" size_t honk_res_stem_wgrad_workspace_bytes(int64_t batch, int32_t c) 
 extern "C" int honk_res_stem_wgrad_f32(const float* x, const float* w0, const float* gy, float* dw, int64_t batch,
                                        int32_t c, int32_t h, int32_t w_, int32_t ph, int32_t pw, void* workspace,
                                        size_t ws_bytes, void* stream) {
-  int rc = stem_check(x, w0, dw, batch, c, h, w_, ph, pw);
-  if (rc) return rc;
+  HONK_TRY(stem_check(x, w0, dw, batch, c, h, w_, ph, pw));
   if (!gy) return fail(HONK_ERR_ARG, "null pointer argument");
   hipStream_t st = (hipStream_t)stream;
   if (batch == 0) {
@@ -2756,6 +2737,6 @@ extern "C" int honk_res_stem_wgrad_f32(const float* x, const float* w0, const fl
   const int n = c * 9;
   hipLaunchKernelGGL(train::wsum_kernel, dim3((unsigned)cdiv(n, train::WSUM_OUT)), dim3(256), 0, st, (const float*)workspace, dw,
                      n, grid);
-  HONK_LAUNCH_CHECK("wsum_kernel");
-  return HONK_OK;
+  return launched("wsum_kernel");
 }
+
