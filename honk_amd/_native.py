@@ -71,6 +71,7 @@ _PROTOS = {
                                                 ctypes.c_void_p]),
     "honk_res_rerun_clips": (ctypes.c_int64, [ctypes.POINTER(ResDesc), ctypes.c_int64]),
     "honk_cnn_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CnnDesc), ctypes.c_int64]),
+    "honk_cnn_launch_plan": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "honk_cnn_forward": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.POINTER(ctypes.c_void_p), c_f32p, c_f32p,
                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "honk_conv2d_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int64] + [ctypes.c_int32] * 9
@@ -253,6 +254,37 @@ def res_launch_plan(desc, batch: int, n_cus: int = 0):
     if n < 0:
         check(n, "honk_res_launch_plan")
     return [KERNEL_NAMES[kinds[i]] for i in range(min(n, 256))]
+
+
+# HONK_CNN_KERNEL_* of include/honk_hip.h (the generic conv GEMM's flags: cnn_kernel_name)
+CNN_KERNEL_NAMES = {1: "conv1x3_kernel", 2: "conv1f_kernel", 3: "conv2x3_kernel", 4: "conv2f_kernel",
+                    5: "maxpool_kernel", 6: "pack_conv2x3_kernel", 7: "pack_conv2f_kernel",
+                    8: "linear_small_kernel<4>", 9: "linear_small_kernel<8>", 10: "linear_small_kernel<16>",
+                    11: "linear_gemm<f32>", 12: "linear_gemm<x3>"}
+CNN_KERNEL_GEMM = 16
+
+
+def cnn_kernel_name(kind: int) -> str:
+    """A HONK_CNN_KERNEL_* code as a name; the generic conv GEMM as
+    ``conv_gemm<f32|x3[,pool2]>[:nhwc-bf16|:nhwc-f32]`` (no suffix: NCHW fp32)."""
+    if kind & CNN_KERNEL_GEMM:
+        flags = kind & ~CNN_KERNEL_GEMM
+        if flags & ~15 or (flags & 12) == 12:
+            raise RuntimeError(f"honk_cnn_launch_plan: unknown kernel kind {kind}")
+        return (f"conv_gemm<{'x3' if flags & 1 else 'f32'}{',pool2' if flags & 2 else ''}>"
+                + (":nhwc-bf16" if flags & 4 else ":nhwc-f32" if flags & 8 else ""))
+    return CNN_KERNEL_NAMES[kind]
+
+
+def cnn_launch_plan(desc):
+    """The launches honk_cnn_forward makes -- the per-call conv2 weight pack (if any), then one
+    chunk's kernels in order -- as names (cnn_kernel_name), under the current HONK_CNN_*
+    environment.  Host-only."""
+    kinds = (ctypes.c_int32 * 16)()
+    n = load().honk_cnn_launch_plan(ctypes.byref(desc), kinds, 16)
+    if n < 0:
+        check(n, "honk_cnn_launch_plan")
+    return [cnn_kernel_name(kinds[i]) for i in range(min(n, 16))]
 
 
 def res_numerics(desc, packed, device):

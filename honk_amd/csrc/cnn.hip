@@ -1068,14 +1068,23 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const float* __restri
   }
 }
 
+// the kernel a Linear of n outputs runs on (HONK_CNN_KERNEL_*)
+static int linear_kind(int n, bool x3) {
+  if (n <= 4) return HONK_CNN_KERNEL_LINEAR_SMALL4;
+  if (n <= 8) return HONK_CNN_KERNEL_LINEAR_SMALL8;
+  if (n <= 16) return HONK_CNN_KERNEL_LINEAR_SMALL16;
+  return x3 ? HONK_CNN_KERNEL_LINEAR_GEMM_X3 : HONK_CNN_KERNEL_LINEAR_GEMM_F32;
+}
+
 static int linear(const float* x, const float* w, const float* b, float* y, int64_t m, int k, int n,
                   int relu, hipStream_t st, bool x3 = false) {
-  if (n <= 16 && m > 0) {
+  const int kind = linear_kind(n, x3);
+  if (kind <= HONK_CNN_KERNEL_LINEAR_SMALL16 && m > 0) {
     constexpr int CPB = 4;
     const unsigned blocks = (unsigned)cdiv(m, CPB);
-    if (n <= 4)
+    if (kind == HONK_CNN_KERNEL_LINEAR_SMALL4)
       hipLaunchKernelGGL((linear_small_kernel<4, CPB>), dim3(blocks), dim3(256), 0, st, x, w, b, y, m, k, n, relu);
-    else if (n <= 8)
+    else if (kind == HONK_CNN_KERNEL_LINEAR_SMALL8)
       hipLaunchKernelGGL((linear_small_kernel<8, CPB>), dim3(blocks), dim3(256), 0, st, x, w, b, y, m, k, n, relu);
     else
       hipLaunchKernelGGL((linear_small_kernel<16, CPB>), dim3(blocks), dim3(256), 0, st, x, w, b, y, m, k, n, relu);
@@ -1444,6 +1453,67 @@ static int64_t chunk_clips(const Shapes& s, int64_t batch) {
   return batch < ch ? batch : ch;
 }
 
+// The forward's launch schedule: the per-call weight pack (L_PACK), then one step per
+// launch of a chunk.  honk_cnn_launch_plan reports it, honk_cnn_workspace_bytes sizes the
+// fragment region from it and honk_cnn_forward runs it: the _applies predicates are asked
+// here and nowhere else.
+enum Layer { L_PACK, L_CONV1, L_POOL1, L_CONV2, L_POOL2, L_LIN, L_DNN1, L_DNN2, L_OUT };
+struct Step {
+  int layer, kind;  // kind: HONK_CNN_KERNEL_*
+};
+struct Plan {
+  Step steps[12];
+  int n = 0;
+  void add(int layer, int kind) { steps[n++] = Step{layer, kind}; }
+  bool has(int kind) const {
+    for (int i = 0; i < n; ++i)
+      if (steps[i].kind == kind) return true;
+    return false;
+  }
+};
+
+static int gemm_kind(bool x3, bool pool2, int nhwc_x3) {
+  return HONK_CNN_KERNEL_GEMM | (x3 ? HONK_CNN_GEMM_X3 : 0) | (pool2 ? HONK_CNN_GEMM_POOL2 : 0) |
+         (nhwc_x3 == 1 ? HONK_CNN_GEMM_NHWC_BF16 : nhwc_x3 == 2 ? HONK_CNN_GEMM_NHWC_F32 : 0);
+}
+
+static Plan plan_forward(const honk_cnn_desc* d, const Shapes& s) {
+  Plan p;
+  const bool x3 = d->precision == HONK_PREC_BF16X3;
+  const bool c2x3 = conv2x3_applies(d, s.ph1, s.pw1, s.oh2, s.ow2);
+  const bool c2f = conv2f_applies(d, s.ph1, s.pw1, s.oh2, s.ow2);
+  if (c2x3) p.add(L_PACK, HONK_CNN_KERNEL_PACK_CONV2X3);  // conv2 weights -> hi/lo fragments
+  if (c2f) p.add(L_PACK, HONK_CNN_KERNEL_PACK_CONV2F);    // conv2 weights -> fp32 fragments
+  // conv1 + ReLU (model.py:187), pool1 (:189; skipped when 1x1)
+  const bool fuse1 = d->p1_h == 2 && d->p1_w == 2;  // conv1 + ReLU + MaxPool2d(2,2) in one kernel
+  if (c2f && conv1f_applies(d, s.oh1, s.ph1, s.pw1))
+    p.add(L_CONV1, HONK_CNN_KERNEL_CONV1F);
+  else if (c2x3 && conv1x3_applies(d, s.oh1, s.ph1, s.pw1))
+    p.add(L_CONV1, HONK_CNN_KERNEL_CONV1X3);
+  else
+    p.add(L_CONV1, gemm_kind(x3, fuse1, c2x3 ? 1 : c2f ? 2 : 0));
+  if (!fuse1 && d->p1_h * d->p1_w > 1) p.add(L_POOL1, HONK_CNN_KERNEL_MAXPOOL);
+  if (c2x3) {  // model.py:190-193 on the fast path (pool2 is 1x1)
+    p.add(L_CONV2, HONK_CNN_KERNEL_CONV2X3);
+  } else if (c2f) {
+    p.add(L_CONV2, HONK_CNN_KERNEL_CONV2F);
+  } else if (d->has_conv2) {
+    const bool fuse2 = d->p2_h == 2 && d->p2_w == 2;
+    p.add(L_CONV2, gemm_kind(x3, fuse2, 0));
+    if (!fuse2 && d->p2_h * d->p2_w > 1) p.add(L_POOL2, HONK_CNN_KERNEL_MAXPOOL);
+  }
+  if (d->has_lin) p.add(L_LIN, linear_kind(32, x3));           // :195-196
+  if (d->dnn1) p.add(L_DNN1, linear_kind(d->dnn1, x3));        // :197-201
+  if (d->dnn2) p.add(L_DNN2, linear_kind(d->dnn2, x3));        // :202-204
+  p.add(L_OUT, linear_kind(d->n_labels, x3));                  // :205
+  return p;
+}
+
+static size_t frag_bytes(const honk_cnn_desc* d, const Plan& p) {
+  return (p.has(HONK_CNN_KERNEL_PACK_CONV2X3) ? conv2x3_frag_bytes(d) : 0) +
+         (p.has(HONK_CNN_KERNEL_PACK_CONV2F) ? conv2f_frag_bytes(d) : 0);
+}
+
 }  // namespace cnn
 }  // namespace honk
 
@@ -1619,10 +1689,24 @@ int honk_conv_same_wgrad_f32(const float* x, const float* dy, float* dw, int64_t
 size_t honk_cnn_workspace_bytes(const honk_cnn_desc* d, int64_t batch) {
   Shapes s;
   if (shapes(d, &s) != HONK_OK || batch < 1) return 0;
-  size_t b = (size_t)2 * chunk_clips(s, batch) * per_clip_floats(s) * sizeof(float);
-  if (conv2x3_applies(d, s.ph1, s.pw1, s.oh2, s.ow2)) b += conv2x3_frag_bytes(d);  // packed conv2 fragments
-  if (conv2f_applies(d, s.ph1, s.pw1, s.oh2, s.ow2)) b += conv2f_frag_bytes(d);
-  return b;
+  return (size_t)2 * chunk_clips(s, batch) * per_clip_floats(s) * sizeof(float) + frag_bytes(d, plan_forward(d, s));
+}
+
+static int check_precision(const honk_cnn_desc* d) {
+  if (d->precision != HONK_PREC_F32 && d->precision != HONK_PREC_BF16X3)
+    return fail(HONK_ERR_UNSUPPORTED, "cnn path precision %d (f32 or bf16x3)", d->precision);
+  return HONK_OK;
+}
+
+int honk_cnn_launch_plan(const honk_cnn_desc* d, int32_t* kinds, int32_t max_kinds) {
+  Shapes s;
+  int rc = shapes(d, &s);
+  if (rc) return rc;
+  rc = check_precision(d);
+  if (rc) return rc;
+  const Plan p = plan_forward(d, s);
+  for (int k = 0; kinds && k < p.n && k < max_kinds; ++k) kinds[k] = p.steps[k].kind;
+  return p.n;
 }
 
 int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float* x, float* logits, int64_t batch,
@@ -1639,167 +1723,124 @@ int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float*
   if (d->dnn1 && (!t[6] || !t[7])) return fail(HONK_ERR_ARG, "dnn1 tensors missing");
   if (d->dnn2 && (!t[8] || !t[9])) return fail(HONK_ERR_ARG, "dnn2 tensors missing");
   if (d->dnn2 && !d->dnn1) return fail(HONK_ERR_ARG, "dnn2 without dnn1");
-  const size_t need = honk_cnn_workspace_bytes(d, batch);
+  const Plan plan = plan_forward(d, s);
+  const int64_t chunk = chunk_clips(s, batch);
+  const size_t need = (size_t)2 * chunk * per_clip_floats(s) * sizeof(float) + frag_bytes(d, plan);
   if (ws_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
-  if (d->precision != HONK_PREC_F32 && d->precision != HONK_PREC_BF16X3)
-    return fail(HONK_ERR_UNSUPPORTED, "cnn path precision %d (f32 or bf16x3)", d->precision);
+  rc = check_precision(d);
+  if (rc) return rc;
   const bool x3 = d->precision == HONK_PREC_BF16X3;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t chunk = chunk_clips(s, batch);
   float* A = (float*)workspace;
   float* B = A + chunk * per_clip_floats(s);
-  const bool c2x3 = conv2x3_applies(d, s.ph1, s.pw1, s.oh2, s.ow2);
   uint4* c2frag = (uint4*)(B + chunk * per_clip_floats(s));
-  if (c2x3) {  // conv2 weights -> hi/lo fragments (one small launch per call)
-    const int ntap = d->c2_kh * d->c2_kw;
-    const int total = 2 * ntap * 4 * 2 * 64 * 8;
-    hipLaunchKernelGGL(pack_conv2x3_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, t[2],
-                       (__bf16*)c2frag, d->c2_out, ntap);
-    HONK_LAUNCH_CHECK("pack_conv2x3_kernel");
-  }
-  const bool c2f = conv2f_applies(d, s.ph1, s.pw1, s.oh2, s.ow2);
-  if (c2f) {  // conv2 weights -> fp32 fragments (one small launch per call)
-    const int ntap = d->c2_kh * d->c2_kw;
-    const int total = 2 * ntap * 2 * 4 * 64 * 4;
-    hipLaunchKernelGGL(pack_conv2f_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, t[2], (float*)c2frag,
-                       d->c2_out, ntap);
-    HONK_LAUNCH_CHECK("pack_conv2f_kernel");
+  const int ntap = d->c2_kh * d->c2_kw;
+  for (int i = 0; i < plan.n; ++i) {  // one small launch per call
+    if (plan.steps[i].kind == HONK_CNN_KERNEL_PACK_CONV2X3) {
+      const int total = 2 * ntap * 4 * 2 * 64 * 8;
+      hipLaunchKernelGGL(pack_conv2x3_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, t[2],
+                         (__bf16*)c2frag, d->c2_out, ntap);
+      HONK_LAUNCH_CHECK("pack_conv2x3_kernel");
+    } else if (plan.steps[i].kind == HONK_CNN_KERNEL_PACK_CONV2F) {
+      const int total = 2 * ntap * 2 * 4 * 64 * 4;
+      hipLaunchKernelGGL(pack_conv2f_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, t[2], (float*)c2frag,
+                         d->c2_out, ntap);
+      HONK_LAUNCH_CHECK("pack_conv2f_kernel");
+    }
   }
 
   for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
     const int64_t n = (batch - c0 < chunk) ? batch - c0 : chunk;
-    const float* xin = x + c0 * d->height * d->width;
-    // conv1 + ReLU (model.py:187) -> A ; pool1 (:189) -> B (skip when 1x1)
-    const bool fuse1 = d->p1_h == 2 && d->p1_w == 2;  // conv1 + ReLU + MaxPool2d(2,2) in one kernel
-    if (c2f && conv1f_applies(d, s.oh1, s.ph1, s.pw1)) {
-      Conv1FArgs c;
-      c.x = xin;
-      c.w = t[0];
-      c.bias = t[1];
-      c.out = A;
-      c.B = (int)n;
-      c.H = d->height;
-      c.W = d->width;
-      c.PH = s.ph1;
-      c.PW = s.pw1;
-      if (n > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
-      const unsigned grid = (unsigned)(n < cu_count() ? n : cu_count());
-      TimedLaunch tl(st, 2.0 * (double)n * s.ph1 * s.pw1 * 4 * 64 * C1X3_KH * C1X3_KW);
-      hipLaunchKernelGGL(conv1f_kernel, dim3(grid), dim3(512), 0, st, c);
-      tl.done(st);
-      HONK_LAUNCH_CHECK("conv1f_kernel");
-    } else if (c2x3 && conv1x3_applies(d, s.oh1, s.ph1, s.pw1)) {
-      Conv1X3Args c;
-      c.x = xin;
-      c.w = t[0];
-      c.bias = t[1];
-      c.out = (__bf16*)A;
-      c.B = (int)n;
-      c.H = d->height;
-      c.W = d->width;
-      c.PH = s.ph1;
-      c.PW = s.pw1;
-      if (n > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
-      const unsigned grid = (unsigned)(n < cu_count() ? n : cu_count());
-      TimedLaunch tl(st, 2.0 * (double)n * s.ph1 * s.pw1 * 4 * 64 * C1X3_KH * C1X3_KW);
-      hipLaunchKernelGGL(conv1x3_kernel, dim3(grid), dim3(512), 0, st, c);
-      tl.done(st);
-      HONK_LAUNCH_CHECK("conv1x3_kernel");
-    } else {
-      rc = conv(xin, t[0], t[1], A, n, 1, d->height, d->width, d->c1_out, d->c1_kh, d->c1_kw, d->c1_sh, d->c1_sw, 1,
-                st, fuse1, x3, c2x3 ? 1 : c2f ? 2 : 0);
-      if (rc) return rc;
-    }
-    const float* cur = A;
-    float* other = B;
-    if (!fuse1 && d->p1_h * d->p1_w > 1) {
-      rc = maxpool(A, B, n * d->c1_out, s.oh1, s.ow1, d->p1_h, d->p1_w, st);
-      if (rc) return rc;
-      cur = B;
-      other = A;
-    }
-    if (c2x3) {  // model.py:190-193 on the fast path (pool2 is 1x1)
-      Conv2X3Args c;
-      c.in = (const __bf16*)A;
-      c.wfrag = c2frag;
-      c.bias = t[3];
-      c.out = B;
-      c.B = (int)n;
-      c.PH = s.ph1;
-      c.PW = s.pw1;
-      c.KW = d->c2_kw;
-      c.ntap = d->c2_kh * d->c2_kw;
-      c.OH = s.oh2;
-      c.OW = s.ow2;
-      c.N = d->c2_out;
-      if (n > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
-      const unsigned grid = (unsigned)(n < cu_count() ? n : cu_count());
-      TimedLaunch tl(st, 2.0 * (double)n * s.oh2 * s.ow2 * d->c2_out * 64 * c.ntap);
-      hipLaunchKernelGGL((conv2x3_kernel<C2X3_MT>), dim3(grid), dim3(256), 0, st, c);
-      tl.done(st);
-      HONK_LAUNCH_CHECK("conv2x3_kernel");
-      cur = B;
-      other = A;
-    } else if (c2f) {  // model.py:190-193, fp32, on the NHWC pooled conv1 output
-      Conv2FArgs c;
-      c.in = A;
-      c.wfrag = (const f32x4*)c2frag;
-      c.bias = t[3];
-      c.out = B;
-      c.B = (int)n;
-      c.PH = s.ph1;
-      c.PW = s.pw1;
-      c.KW = d->c2_kw;
-      c.ntap = d->c2_kh * d->c2_kw;
-      c.OH = s.oh2;
-      c.OW = s.ow2;
-      c.N = d->c2_out;
-      if (n > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
-      const unsigned grid = (unsigned)(n < cu_count() ? n : cu_count());
-      TimedLaunch tl(st, 2.0 * (double)n * s.oh2 * s.ow2 * d->c2_out * 64 * c.ntap);
-      hipLaunchKernelGGL((conv2f_kernel<C2F_MT>), dim3(grid), dim3(256), 0, st, c);
-      tl.done(st);
-      HONK_LAUNCH_CHECK("conv2f_kernel");
-      cur = B;
-      other = A;
-    } else if (d->has_conv2) {  // model.py:190-193
-      const bool fuse2 = d->p2_h == 2 && d->p2_w == 2;
-      rc = conv(cur, t[2], t[3], other, n, d->c1_out, s.ph1, s.pw1, d->c2_out, d->c2_kh, d->c2_kw, d->c2_sh,
-                d->c2_sw, 1, st, fuse2, x3);
-      if (rc) return rc;
-      const float* c2 = other;
-      float* o2 = (float*)cur;
-      if (!fuse2 && d->p2_h * d->p2_w > 1) {
-        rc = maxpool(c2, o2, n * d->c2_out, s.oh2, s.ow2, d->p2_h, d->p2_w, st);
-        if (rc) return rc;
-        cur = o2;
-        other = (float*)c2;
-      } else {
-        cur = c2;
-        other = o2;
+    if (n > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
+    const unsigned grid = (unsigned)(n < cu_count() ? n : cu_count());  // the dedicated kernels' persistent grid
+    // ping-pong: every step reads cur and writes other (conv1: x -> A); flatten is free: NCHW (model.py:194)
+    const float* cur = x + c0 * d->height * d->width;
+    float* other = A;
+    int width = s.flat;
+    auto wrote = [&]() {  // a step's output is the next one's input
+      cur = other;
+      other = (cur == A) ? B : A;
+    };
+    for (int i = 0; i < plan.n; ++i) {
+      const int kind = plan.steps[i].kind;
+      const bool gemm = (kind & HONK_CNN_KERNEL_GEMM) != 0;
+      const bool pool = gemm && (kind & HONK_CNN_GEMM_POOL2);
+      rc = HONK_OK;
+      switch (plan.steps[i].layer) {
+        case L_PACK:
+          continue;
+        case L_CONV1:
+          if (kind == HONK_CNN_KERNEL_CONV1F) {
+            Conv1FArgs c;
+            c.x = cur; c.w = t[0]; c.bias = t[1]; c.out = other;
+            c.B = (int)n; c.H = d->height; c.W = d->width; c.PH = s.ph1; c.PW = s.pw1;
+            TimedLaunch tl(st, 2.0 * (double)n * s.ph1 * s.pw1 * 4 * 64 * C1X3_KH * C1X3_KW);
+            hipLaunchKernelGGL(conv1f_kernel, dim3(grid), dim3(512), 0, st, c);
+            tl.done(st);
+            HONK_LAUNCH_CHECK("conv1f_kernel");
+          } else if (kind == HONK_CNN_KERNEL_CONV1X3) {
+            Conv1X3Args c;
+            c.x = cur; c.w = t[0]; c.bias = t[1]; c.out = (__bf16*)other;
+            c.B = (int)n; c.H = d->height; c.W = d->width; c.PH = s.ph1; c.PW = s.pw1;
+            TimedLaunch tl(st, 2.0 * (double)n * s.ph1 * s.pw1 * 4 * 64 * C1X3_KH * C1X3_KW);
+            hipLaunchKernelGGL(conv1x3_kernel, dim3(grid), dim3(512), 0, st, c);
+            tl.done(st);
+            HONK_LAUNCH_CHECK("conv1x3_kernel");
+          } else {
+            rc = conv(cur, t[0], t[1], other, n, 1, d->height, d->width, d->c1_out, d->c1_kh, d->c1_kw, d->c1_sh,
+                      d->c1_sw, 1, st, pool, x3,
+                      (kind & HONK_CNN_GEMM_NHWC_BF16) ? 1 : (kind & HONK_CNN_GEMM_NHWC_F32) ? 2 : 0);
+          }
+          break;
+        case L_POOL1:
+          rc = maxpool(cur, other, n * d->c1_out, s.oh1, s.ow1, d->p1_h, d->p1_w, st);
+          break;
+        case L_CONV2:
+          if (kind == HONK_CNN_KERNEL_CONV2X3) {  // on the NHWC hi/lo pooled conv1 output
+            Conv2X3Args c;
+            c.in = (const __bf16*)cur; c.wfrag = c2frag; c.bias = t[3]; c.out = other;
+            c.B = (int)n; c.PH = s.ph1; c.PW = s.pw1; c.KW = d->c2_kw; c.ntap = ntap;
+            c.OH = s.oh2; c.OW = s.ow2; c.N = d->c2_out;
+            TimedLaunch tl(st, 2.0 * (double)n * s.oh2 * s.ow2 * d->c2_out * 64 * ntap);
+            hipLaunchKernelGGL((conv2x3_kernel<C2X3_MT>), dim3(grid), dim3(256), 0, st, c);
+            tl.done(st);
+            HONK_LAUNCH_CHECK("conv2x3_kernel");
+          } else if (kind == HONK_CNN_KERNEL_CONV2F) {  // fp32, on the NHWC pooled conv1 output
+            Conv2FArgs c;
+            c.in = cur; c.wfrag = (const f32x4*)c2frag; c.bias = t[3]; c.out = other;
+            c.B = (int)n; c.PH = s.ph1; c.PW = s.pw1; c.KW = d->c2_kw; c.ntap = ntap;
+            c.OH = s.oh2; c.OW = s.ow2; c.N = d->c2_out;
+            TimedLaunch tl(st, 2.0 * (double)n * s.oh2 * s.ow2 * d->c2_out * 64 * ntap);
+            hipLaunchKernelGGL((conv2f_kernel<C2F_MT>), dim3(grid), dim3(256), 0, st, c);
+            tl.done(st);
+            HONK_LAUNCH_CHECK("conv2f_kernel");
+          } else {
+            rc = conv(cur, t[2], t[3], other, n, d->c1_out, s.ph1, s.pw1, d->c2_out, d->c2_kh, d->c2_kw, d->c2_sh,
+                      d->c2_sw, 1, st, pool, x3);
+          }
+          break;
+        case L_POOL2:
+          rc = maxpool(cur, other, n * d->c2_out, s.oh2, s.ow2, d->p2_h, d->p2_w, st);
+          break;
+        case L_LIN:
+          rc = linear(cur, t[4], t[5], other, n, width, 32, 0, st, x3);
+          width = 32;
+          break;
+        case L_DNN1:
+          rc = linear(cur, t[6], t[7], other, n, width, d->dnn1, d->dnn1_relu, st, x3);
+          width = d->dnn1;
+          break;
+        case L_DNN2:
+          rc = linear(cur, t[8], t[9], other, n, width, d->dnn2, 0, st, x3);
+          width = d->dnn2;
+          break;
+        case L_OUT:
+          rc = linear(cur, t[10], t[11], logits + c0 * d->n_labels, n, width, d->n_labels, 0, st, x3);
+          break;
       }
-    }
-    int width = s.flat;  // flatten is free: NCHW (model.py:194)
-    if (d->has_lin) {    // :195-196
-      rc = linear(cur, t[4], t[5], other, n, width, 32, 0, st, x3);
       if (rc) return rc;
-      width = 32;
-      float* tmp = other; other = (float*)cur; cur = tmp;
+      wrote();
     }
-    if (d->dnn1) {       // :197-201
-      rc = linear(cur, t[6], t[7], other, n, width, d->dnn1, d->dnn1_relu, st, x3);
-      if (rc) return rc;
-      width = d->dnn1;
-      float* tmp = other; other = (float*)cur; cur = tmp;
-    }
-    if (d->dnn2) {       // :202-204
-      rc = linear(cur, t[8], t[9], other, n, width, d->dnn2, 0, st, x3);
-      if (rc) return rc;
-      width = d->dnn2;
-      float* tmp = other; other = (float*)cur; cur = tmp;
-    }
-    rc = linear(cur, t[10], t[11], logits + c0 * d->n_labels, n, width, d->n_labels, 0, st, x3);  // :205
-    if (rc) return rc;
   }
   return HONK_OK;
 }

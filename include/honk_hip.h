@@ -222,6 +222,36 @@ typedef struct honk_cnn_desc {
 
 size_t honk_cnn_workspace_bytes(const honk_cnn_desc* d, int64_t batch);
 /*
+ * The launches honk_cnn_forward makes, in order: kinds[i] = HONK_CNN_KERNEL_* (up to max_kinds
+ * written) -- first the per-call weight pack of a dedicated conv2 kernel (if one runs), then
+ * what every chunk of clips launches: conv1, [pool1], [conv2, [pool2]], [lin], [dnn1], [dnn2],
+ * output.  Returns the launch count (> 0), or a (negative) HONK_ERR_* status code.  The forward
+ * runs the very list this reports, under the same HONK_CNN_C1F / C1X3 / C2F / C2X3 switches
+ * (= 0: that dedicated kernel off).  Host-only; no GPU work.
+ *
+ * The generic implicit GEMM of a conv is HONK_CNN_KERNEL_GEMM plus flags: its precision, the
+ * fused 2x2 max-pool, and the layout it stores (NCHW fp32, or the NHWC input of the dedicated
+ * conv2 kernels).  A Linear with > 16 outputs is the same GEMM, reported as LINEAR_GEMM_*.
+ */
+#define HONK_CNN_KERNEL_CONV1X3 1        /* conv1x3_kernel (bf16x3 conv1 + ReLU + 2x2 pool)     */
+#define HONK_CNN_KERNEL_CONV1F 2         /* conv1f_kernel  (fp32   conv1 + ReLU + 2x2 pool)     */
+#define HONK_CNN_KERNEL_CONV2X3 3        /* conv2x3_kernel<13>                                  */
+#define HONK_CNN_KERNEL_CONV2F 4         /* conv2f_kernel<13>                                   */
+#define HONK_CNN_KERNEL_MAXPOOL 5        /* maxpool_kernel (a pool the conv's GEMM did not fuse) */
+#define HONK_CNN_KERNEL_PACK_CONV2X3 6   /* pack_conv2x3_kernel                                 */
+#define HONK_CNN_KERNEL_PACK_CONV2F 7    /* pack_conv2f_kernel                                  */
+#define HONK_CNN_KERNEL_LINEAR_SMALL4 8  /* linear_small_kernel<4, 4>   (<= 4 outputs)          */
+#define HONK_CNN_KERNEL_LINEAR_SMALL8 9  /* linear_small_kernel<8, 4>   (5 .. 8)                */
+#define HONK_CNN_KERNEL_LINEAR_SMALL16 10 /* linear_small_kernel<16, 4> (9 .. 16)               */
+#define HONK_CNN_KERNEL_LINEAR_GEMM_F32 11 /* conv_gemm_kernel<false, false> as a Linear        */
+#define HONK_CNN_KERNEL_LINEAR_GEMM_X3 12  /* conv_gemm_kernel<false, true>  as a Linear        */
+#define HONK_CNN_KERNEL_GEMM 16          /* conv_gemm_kernel of a conv, or-ed with:             */
+#define HONK_CNN_GEMM_X3 1               /*   bf16x3 operands (else fp32)                       */
+#define HONK_CNN_GEMM_POOL2 2            /*   fused 2x2 max-pool                                */
+#define HONK_CNN_GEMM_NHWC_BF16 4        /*   stores [B][PH][PW][hi N | lo N] bf16 (conv2x3's input) */
+#define HONK_CNN_GEMM_NHWC_F32 8         /*   stores [B][PH][PW][N] fp32 (conv2f's input)       */
+int honk_cnn_launch_plan(const honk_cnn_desc* d, int32_t* kinds, int32_t max_kinds);
+/*
  * tensors[] (device fp32, contiguous; NULL for absent layers), fixed order of 12:
  *   conv1.weight, conv1.bias, conv2.weight, conv2.bias, lin.weight, lin.bias,
  *   dnn1.weight, dnn1.bias, dnn2.weight, dnn2.bias, output.weight, output.bias
