@@ -46,6 +46,15 @@ class MfccWindowsPlan(ctypes.Structure):
         ("shared", ctypes.c_int32), ("frames", ctypes.c_int32)]
 
 
+class FrontPlan(ctypes.Structure):
+    """honk_front_plan_t."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("route", "frames", "n_bins", "launches")] + [
+        ("lds_bytes", ctypes.c_int64)]
+
+
+FRONT_ROUTES = {1: "mfma", 2: "valu"}  # HONK_FRONT_ROUTE_*
+
+
 class PcenParams(ctypes.Structure):
     """honk_pcen_params_t (defaults: HONK_PCEN_* of include/honk_hip.h)."""
     _fields_ = [(n, ctypes.c_float) for n in ("eps", "s", "alpha", "delta", "r")] + [("power", ctypes.c_int32)]
@@ -147,6 +156,8 @@ _PROTOS = {
                                 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "honk_mfcc_f32": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                      c_f32p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p, ctypes.c_void_p]),
+    "honk_mfcc_plan": (ctypes.c_int, [ctypes.c_int32] * 5 + [ctypes.c_void_p]),
+    "honk_pcen_plan": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.c_void_p]),
     "honk_mfcc_windows_plan": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_int64] * 2
                                + [ctypes.c_void_p]),
     "honk_mfcc_windows_i16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
@@ -285,6 +296,17 @@ def cnn_launch_plan(desc):
     if n < 0:
         check(n, "honk_cnn_launch_plan")
     return [cnn_kernel_name(kinds[i]) for i in range(min(n, 16))]
+
+
+def front_plan(samples, n_fft, hop, n_mels, n_dct=None):
+    """honk_mfcc_plan (n_dct given) or honk_pcen_plan (n_dct None) under the current HONK_MFCC_VALU
+    environment -> (status, FrontPlan); the plan is filled where status is 0.  Host-only."""
+    plan, lib = FrontPlan(), load()
+    if n_dct is None:
+        rc = lib.honk_pcen_plan(int(samples), int(n_fft), int(hop), int(n_mels), ctypes.addressof(plan))
+    else:
+        rc = lib.honk_mfcc_plan(int(samples), int(n_fft), int(hop), int(n_mels), int(n_dct), ctypes.addressof(plan))
+    return rc, plan
 
 
 def res_numerics(desc, packed, device):

@@ -87,6 +87,11 @@ class AudioPreprocessor(object):
         n = np.arange(n_fft)
         self._window = (0.5 - 0.5 * np.cos(2.0 * np.pi * n / n_fft)).astype(np.float32)
 
+    def n_frames(self, samples):
+        """Frames of a centre-padded clip (csrc/mfcc_spectrum.h centre_frames): 1 + samples // hop for
+        even n_fft; for odd n_fft the padded clip is one sample shorter than samples + n_fft."""
+        return 1 + (int(samples) + 2 * (self.n_fft // 2) - self.n_fft) // self.hop_length
+
     def _stft(self, y):
         y = np.asarray(y, dtype=np.float32)
         pad = self.n_fft // 2
@@ -135,7 +140,7 @@ class AudioPreprocessor(object):
             data = data[None]
         if data.ndim != 2:
             raise ValueError("compute_pcen: data must be [S], [1, S] or [B, S]")
-        frames = 1 + data.shape[1] // self.hop_length
+        frames = self.n_frames(data.shape[1])
         out = np.empty((data.shape[0], frames, self.n_mels), np.float32)
         for i, y in enumerate(data):
             out[i] = self._pcen_clip(y)
@@ -151,7 +156,7 @@ class AudioPreprocessor(object):
         pcm = pcm.contiguous().float()
         B, S = pcm.shape
         win, mel, _ = self._device_tables(pcm.device)
-        frames = 1 + S // self.hop_length
+        frames = self.n_frames(S)
         out = torch.empty(B, frames, mel.shape[0], dtype=torch.float32, device=pcm.device)
         p = self.pcen_params
         params = _native.PcenParams(p["eps"], p["s"], p["alpha"], p["delta"], p["r"], int(p["power"]))
@@ -185,7 +190,7 @@ class AudioPreprocessor(object):
         pcm = pcm.contiguous().float()
         B, S = pcm.shape
         win, mel, dct = self._device_tables(pcm.device)
-        frames = 1 + S // self.hop_length
+        frames = self.n_frames(S)
         out = torch.empty(B, frames, dct.shape[0], dtype=torch.float32, device=pcm.device)
         lib = _native.load()
         with torch.cuda.device(pcm.device):
@@ -226,7 +231,7 @@ class AudioPreprocessor(object):
         count = max(0, W - first) if count is None else int(count)
         if count < 0 or first + count > W:
             raise ValueError(f"compute_mfccs_windows: windows [{first}, {first + count}) of {W}")
-        frames, n_dct = 1 + window // self.hop_length, self.dct_filters.shape[0]
+        frames, n_dct = self.n_frames(window), self.dct_filters.shape[0]
         if not pcm.is_cuda:
             x = pcm.numpy()
             if count == 0:

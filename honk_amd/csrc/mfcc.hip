@@ -71,36 +71,41 @@ __global__ __launch_bounds__(64 * MF_WAVES) void mfcc_mfma_kernel(MfmaArgs ma) {
 
 using namespace honk;
 
+extern "C" int honk_mfcc_plan(int32_t samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_dct,
+                              honk_front_plan_t* plan) {
+  if (!plan) return fail(HONK_ERR_ARG, "null pointer argument");
+  mfcc::FrontPlan fp;
+  const int rc = mfcc::front_plan(mfcc::FRONT_MFCC, samples, n_fft, hop, n_mels, n_dct, &fp);
+  if (rc != HONK_OK) return rc;
+  *plan = fp.p;
+  return HONK_OK;
+}
+
 extern "C" int honk_mfcc_f32(const float* pcm, int64_t batch, int32_t samples, const float* window,
                              int32_t n_fft, int32_t hop, const float* mel_weights, int32_t n_mels,
                              const float* dct, int32_t n_dct, float* out, void* stream) {
-  if (batch < 0 || samples < 1 || n_fft < 2 || hop < 1 || n_mels < 1 || n_dct < 1)
-    return fail(HONK_ERR_ARG, "bad mfcc arguments");
+  if (batch < 0) return fail(HONK_ERR_ARG, "bad mfcc arguments");
+  // the shape checks, route, frame count and LDS bytes: front_plan (mfcc_spectrum.h), which honk_mfcc_plan reports
+  mfcc::FrontPlan fp;
+  const int rc = mfcc::front_plan(mfcc::FRONT_MFCC, samples, n_fft, hop, n_mels, n_dct, &fp);
+  if (rc != HONK_OK) return rc;
   if (batch == 0) return HONK_OK;
   if (!pcm || !window || !mel_weights || !dct || !out) return fail(HONK_ERR_ARG, "null pointer argument");
-  if (n_fft / 2 >= samples) return fail(HONK_ERR_ARG, "reflect padding needs samples > n_fft/2");
   if (batch > 65535) return fail(HONK_ERR_ARG, "batch > 65535 per call");
   mfcc::Args a;
   a.pcm = pcm; a.window = window; a.melw = mel_weights; a.dct = dct; a.out = out;
-  a.S = samples; a.n_fft = n_fft; a.hop = hop; a.n_bins = n_fft / 2 + 1; a.n_mels = n_mels; a.n_dct = n_dct;
-  a.frames = 1 + samples / hop;  // centre padding: 1 + (S + 2*(n_fft/2) - n_fft) / hop for even n_fft
-  // MFMA path: frames <= 112, n_fft and hop multiples of 16 / 4, its LDS plan fits
-  {
-    mfcc::MfmaArgs ma;
-    size_t lds;
-    mfcc::mfma_plan(a, &ma, &lds);
-    if (mfcc::mfma_shape_ok(a) && lds <= 160 * 1024 && !getenv("HONK_MFCC_VALU")) {
-      if (lds > 64 * 1024) HONK_HIP_CHECK(hipFuncSetAttribute((const void*)mfcc::mfcc_mfma_kernel,
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(mfcc::mfcc_mfma_kernel, dim3((unsigned)batch), dim3(64 * mfcc::MF_WAVES), lds,
-                         (hipStream_t)stream, ma);
-      HONK_LAUNCH_CHECK("mfcc_mfma_kernel");
-      return HONK_OK;
-    }
+  a.S = samples; a.n_fft = n_fft; a.hop = hop; a.n_bins = fp.p.n_bins; a.n_mels = n_mels; a.n_dct = n_dct;
+  a.frames = fp.p.frames;
+  const size_t lds = (size_t)fp.p.lds_bytes;
+  if (fp.p.route == HONK_FRONT_ROUTE_MFMA) {
+    fp.ma.a = a;
+    if (lds > mfcc::LDS_OPTIN) HONK_HIP_CHECK(hipFuncSetAttribute((const void*)mfcc::mfcc_mfma_kernel,
+                                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(mfcc::mfcc_mfma_kernel, dim3((unsigned)batch), dim3(64 * mfcc::MF_WAVES), lds,
+                       (hipStream_t)stream, fp.ma);
+    HONK_LAUNCH_CHECK("mfcc_mfma_kernel");
+    return HONK_OK;
   }
-  const int span = (mfcc::FPB - 1) * hop + n_fft;
-  const size_t lds = sizeof(float) * ((size_t)span + 2 * n_fft + mfcc::FPB * (a.n_bins + n_mels));
-  if (lds > 64 * 1024) return fail(HONK_ERR_UNSUPPORTED, "mfcc: n_fft too large for the LDS plan");
   dim3 grid((unsigned)cdiv(a.frames, mfcc::FPB), (unsigned)batch);
   hipLaunchKernelGGL(mfcc::mfcc_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
   HONK_LAUNCH_CHECK("mfcc_kernel");

@@ -5,6 +5,8 @@
 #pragma once
 #include "common.h"
 
+#include <cstdlib>
+
 namespace honk {
 namespace mfcc {
 
@@ -100,14 +102,74 @@ struct MfmaArgs {
   int xp;      // floats of the padded signal image
 };
 
-// what the host sizes the MFMA route with: the shape test and the stage's LDS bytes
-inline bool mfma_shape_ok(const Args& a) { return a.frames <= MF_MT * 16 && a.n_fft % 16 == 0 && a.hop % 4 == 0; }
-inline void mfma_plan(const Args& a, MfmaArgs* ma, size_t* lds) {
-  ma->a = a;
-  ma->ntiles = (int)cdiv(2 * a.n_bins, 16);
-  ma->xp = (MF_MT * 16 - 1) * a.hop + a.n_fft;
-  *lds = sizeof(float) * ((size_t)ma->xp + 3 * a.n_fft + (size_t)a.n_mels * a.n_bins + MF_MT * 16 * a.n_mels) +
-         sizeof(int) * a.n_bins;
+// ---- the host's one route decision (honk_mfcc_f32, honk_pcen_f32 and their plan queries) ---- //
+// frames of a centre-padded clip: n_fft/2 reflected samples on either side, so 1 + samples/hop
+// for even n_fft; for odd n_fft the padded clip is one sample shorter than samples + n_fft
+inline int centre_frames(int samples, int n_fft, int hop) {
+  return (int)(1 + ((int64_t)samples + 2 * (n_fft / 2) - n_fft) / hop);
+}
+
+// ORDERED: the floats the fixed-order mel accumulation takes after the MFMA stage's own -- the
+// |X|^POWER of one round of MF_WAVES column tiles [MF_MT*16][PW_STRIDE], then each band's
+// bin range [n_mels]
+constexpr int PW_STRIDE = 8 * MF_WAVES + 1;
+__host__ __device__ inline int ordered_floats(int n_mels) { return MF_MT * 16 * PW_STRIDE + n_mels; }
+
+enum Front { FRONT_MFCC = 0, FRONT_PCEN = 1 };
+constexpr size_t LDS_OPTIN = 64 * 1024;   // above it a launch asks for the dynamic LDS first
+constexpr size_t LDS_MFMA = 160 * 1024;   // the MFMA route's ceiling
+constexpr size_t LDS_VALU = 64 * 1024;    // the VALU route's
+
+struct FrontPlan {
+  honk_front_plan_t p;  // what the plan queries report; p.lds_bytes is the main kernel's launch size
+  MfmaArgs ma;          // MFMA route: ntiles, xp (ma.a is the caller's to fill)
+  int nseg, extra_off;  // fused PCEN: scan segments per band, float offset of the ordered stage
+};
+
+// Route, frame count and LDS bytes of one front-end call; status and reason as the launch
+// returns them.  Host-only, reads HONK_MFCC_VALU.  (PCEN: n_dct = n_mels.)
+inline int front_plan(Front fe, int32_t samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_dct,
+                      FrontPlan* fp) {
+  const char* what = fe == FRONT_PCEN ? "pcen" : "mfcc";
+  if (samples < 1 || n_fft < 2 || hop < 1 || n_mels < 1 || n_dct < 1) return fail(HONK_ERR_ARG, "bad %s arguments", what);
+  if (n_fft / 2 >= samples) return fail(HONK_ERR_ARG, "reflect padding needs samples > n_fft/2");
+  const int64_t n_bins = n_fft / 2 + 1;
+  const int frames = centre_frames(samples, n_fft, hop);
+  fp->p.frames = frames;
+  fp->p.n_bins = (int32_t)n_bins;
+  fp->nseg = 0;
+  fp->extra_off = 0;
+  // MFMA route: frames <= 112, n_fft and hop multiples of 16 / 4, its LDS plan fits
+  if (frames <= MF_MT * 16 && n_fft % 16 == 0 && hop % 4 == 0 && !getenv("HONK_MFCC_VALU")) {
+    size_t lds = sizeof(float) * ((size_t)(MF_MT * 16 - 1) * hop + 4 * (size_t)n_fft + (size_t)n_mels * n_bins +
+                                  (size_t)MF_MT * 16 * n_mels) + sizeof(int) * (size_t)n_bins;
+    int nseg = 0;
+    size_t extra_off = 0;
+    if (fe == FRONT_PCEN && lds <= LDS_MFMA) {  // the ordered mel stage and the scan's [nseg][n_mels] summaries
+      nseg = n_mels >= 64 * MF_WAVES ? 1 : 64 * MF_WAVES / n_mels;
+      extra_off = (lds + sizeof(float) - 1) / sizeof(float);
+      lds = sizeof(float) * (extra_off + ordered_floats(n_mels) + (size_t)nseg * n_mels);
+    }
+    if (lds <= LDS_MFMA) {
+      fp->nseg = nseg;
+      fp->extra_off = (int)extra_off;
+      fp->ma.ntiles = (int)cdiv(2 * n_bins, 16);
+      fp->ma.xp = (MF_MT * 16 - 1) * hop + n_fft;  // floats of the padded signal image
+      fp->p.route = HONK_FRONT_ROUTE_MFMA;
+      fp->p.launches = 1;
+      fp->p.lds_bytes = (int64_t)lds;
+      return HONK_OK;
+    }
+  }
+  // VALU route: the spectrum stage's floats (valu_spectrum_floats, in size_t), and the MFCC's
+  // [FPB][n_mels] log-mel tile
+  const size_t lds = sizeof(float) * ((size_t)(FPB - 1) * hop + 3 * (size_t)n_fft + FPB * (size_t)n_bins +
+                                      (fe == FRONT_MFCC ? FPB * (size_t)n_mels : 0));
+  if (lds > LDS_VALU) return fail(HONK_ERR_UNSUPPORTED, "%s: n_fft too large for the LDS plan", what);
+  fp->p.route = HONK_FRONT_ROUTE_VALU;
+  fp->p.launches = fe == FRONT_PCEN ? 2 : 1;
+  fp->p.lds_bytes = (int64_t)lds;
+  return HONK_OK;
 }
 
 // One column tile t of the GEMM for this wave: acc[m] = D[16 t + 4 g + r][16 m + i16].
@@ -144,14 +206,8 @@ __device__ __forceinline__ void mfma_tile(const Args& a, const float* xpad, cons
   }
 }
 
-// ORDERED: the floats the fixed-order mel accumulation takes after mfma_plan's bytes -- the
-// |X|^POWER of one round of MF_WAVES column tiles [MF_MT*16][PW_STRIDE], then each band's
-// bin range [n_mels]
-constexpr int PW_STRIDE = 8 * MF_WAVES + 1;
-__host__ __device__ inline int ordered_floats(int n_mels) { return MF_MT * 16 * PW_STRIDE + n_mels; }
-
 // Clip blockIdx.x's mel energies: returns melacc [MF_MT*16][n_mels] in smf (rows < frames
-// valid), synchronised.  blockDim.x = 64 * MF_WAVES; smf holds mfma_plan's bytes.
+// valid), synchronised.  blockDim.x = 64 * MF_WAVES; smf holds front_plan's bytes.
 // ORDERED = false: |X|^POWER goes straight into the mel bins by LDS float atomics (the
 // order the waves arrive in: equal to rounding from run to run).  ORDERED = true: each
 // round of MF_WAVES tiles parks |X|^POWER in `extra` (ordered_floats) and every (frame,

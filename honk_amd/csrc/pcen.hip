@@ -92,8 +92,7 @@ __device__ __forceinline__ void scan_bands(float* e, int F, int stride, int band
 }
 
 // ---- fused route ------------------------------------------------------------------ //
-constexpr int FUSED_THREADS = 64 * mfcc::MF_WAVES;
-inline int fused_segments(int n_mels) { return n_mels >= FUSED_THREADS ? 1 : FUSED_THREADS / n_mels; }
+constexpr int FUSED_THREADS = 64 * mfcc::MF_WAVES;  // (front_plan: FUSED_THREADS / n_mels scan segments per band)
 
 template <int POWER>
 __global__ __launch_bounds__(FUSED_THREADS) void pcen_mfma_kernel(MfmaArgs ma, Params p, int nseg, int extra_off) {
@@ -137,25 +136,21 @@ __global__ __launch_bounds__(SCAN_THREADS) void pcen_scan_kernel(float* out, int
   scan_bands(out + (int64_t)blockIdx.y * F * NM, F, NM, band0, nb, SCAN_SEGS, summ, p);
 }
 
+// route, frame count and LDS bytes come from front_plan (mfcc_spectrum.h), which honk_pcen_plan reports
 template <int POWER>
-static int launch(const Args& a, const Params& p, int64_t batch, hipStream_t stream) {
-  MfmaArgs ma;
-  size_t lds;
-  mfcc::mfma_plan(a, &ma, &lds);
-  const int nseg = fused_segments(a.n_mels);
-  const int extra_off = (int)((lds + sizeof(float) - 1) / sizeof(float));
-  lds = sizeof(float) * ((size_t)extra_off + mfcc::ordered_floats(a.n_mels) + (size_t)nseg * a.n_mels);
-  if (mfcc::mfma_shape_ok(a) && lds <= 160 * 1024 && !getenv("HONK_MFCC_VALU")) {
-    if (lds > 64 * 1024)
+static int launch(const Args& a, const mfcc::FrontPlan& fp, const Params& p, int64_t batch, hipStream_t stream) {
+  const size_t lds = (size_t)fp.p.lds_bytes;
+  if (fp.p.route == HONK_FRONT_ROUTE_MFMA) {
+    MfmaArgs ma = fp.ma;
+    ma.a = a;
+    if (lds > mfcc::LDS_OPTIN)
       HONK_HIP_CHECK(hipFuncSetAttribute((const void*)pcen_mfma_kernel<POWER>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(pcen_mfma_kernel<POWER>, dim3((unsigned)batch), dim3(FUSED_THREADS), lds, stream, ma, p, nseg,
-                       extra_off);
+    hipLaunchKernelGGL(pcen_mfma_kernel<POWER>, dim3((unsigned)batch), dim3(FUSED_THREADS), lds, stream, ma, p, fp.nseg,
+                       fp.extra_off);
     HONK_LAUNCH_CHECK("pcen_mfma_kernel");
     return HONK_OK;
   }
-  lds = sizeof(float) * (size_t)mfcc::valu_spectrum_floats(a.n_fft, a.hop, a.n_bins);
-  if (lds > 64 * 1024) return fail(HONK_ERR_UNSUPPORTED, "pcen: n_fft too large for the LDS plan");
   hipLaunchKernelGGL(pcen_energy_kernel<POWER>, dim3((unsigned)cdiv(a.frames, FPB), (unsigned)batch), dim3(256), lds,
                      stream, a);
   HONK_LAUNCH_CHECK("pcen_energy_kernel");
@@ -170,11 +165,22 @@ static int launch(const Args& a, const Params& p, int64_t batch, hipStream_t str
 
 using namespace honk;
 
+extern "C" int honk_pcen_plan(int32_t samples, int32_t n_fft, int32_t hop, int32_t n_mels, honk_front_plan_t* plan) {
+  if (!plan) return fail(HONK_ERR_ARG, "null pointer argument");
+  mfcc::FrontPlan fp;
+  const int rc = mfcc::front_plan(mfcc::FRONT_PCEN, samples, n_fft, hop, n_mels, n_mels, &fp);
+  if (rc != HONK_OK) return rc;
+  *plan = fp.p;
+  return HONK_OK;
+}
+
 extern "C" int honk_pcen_f32(const float* pcm, int64_t batch, int32_t samples, const float* window, int32_t n_fft,
                              int32_t hop, const float* mel_weights, int32_t n_mels,
                              const honk_pcen_params_t* params, float* out, void* stream) {
-  if (batch < 0 || samples < 1 || n_fft < 2 || hop < 1 || n_mels < 1)
-    return fail(HONK_ERR_ARG, "bad pcen arguments");
+  if (batch < 0) return fail(HONK_ERR_ARG, "bad pcen arguments");
+  mfcc::FrontPlan fp;
+  const int rc = mfcc::front_plan(mfcc::FRONT_PCEN, samples, n_fft, hop, n_mels, n_mels, &fp);
+  if (rc != HONK_OK) return rc;
   honk_pcen_params_t q = {HONK_PCEN_EPS, HONK_PCEN_S, HONK_PCEN_ALPHA, HONK_PCEN_DELTA, HONK_PCEN_R, HONK_PCEN_POWER};
   if (params) q = *params;
   if (!std::isfinite(q.eps) || !std::isfinite(q.s) || !std::isfinite(q.alpha) || !std::isfinite(q.delta) ||
@@ -188,13 +194,12 @@ extern "C" int honk_pcen_f32(const float* pcm, int64_t batch, int32_t samples, c
   if (q.power != 1 && q.power != 2) return fail(HONK_ERR_ARG, "pcen: power must be 1 or 2");
   if (batch == 0) return HONK_OK;
   if (!pcm || !window || !mel_weights || !out) return fail(HONK_ERR_ARG, "null pointer argument");
-  if (n_fft / 2 >= samples) return fail(HONK_ERR_ARG, "reflect padding needs samples > n_fft/2");
   if (batch > 65535) return fail(HONK_ERR_ARG, "batch > 65535 per call");
   mfcc::Args a;
   a.pcm = pcm; a.window = window; a.melw = mel_weights; a.dct = nullptr; a.out = out;
-  a.S = samples; a.n_fft = n_fft; a.hop = hop; a.n_bins = n_fft / 2 + 1; a.n_mels = n_mels; a.n_dct = n_mels;
-  a.frames = 1 + samples / hop;
+  a.S = samples; a.n_fft = n_fft; a.hop = hop; a.n_bins = fp.p.n_bins; a.n_mels = n_mels; a.n_dct = n_mels;
+  a.frames = fp.p.frames;
   const pcen::Params p = {q.eps, q.s, q.alpha, q.delta, q.r};
-  return q.power == 1 ? pcen::launch<1>(a, p, batch, (hipStream_t)stream)
-                      : pcen::launch<2>(a, p, batch, (hipStream_t)stream);
+  return q.power == 1 ? pcen::launch<1>(a, fp, p, batch, (hipStream_t)stream)
+                      : pcen::launch<2>(a, fp, p, batch, (hipStream_t)stream);
 }

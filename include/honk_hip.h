@@ -319,15 +319,43 @@ int honk_conv_same_wgrad_f32(const float* x, const float* dy, float* dw, int64_t
 
 /* ---- MFCC front-end (AudioPreprocessor.compute_mfccs, utils/manage_audio.py:30-42) ---- */
 /*
- * pcm [batch][samples] f32 -> out [batch][1 + samples/hop][n_dct] f32 (the
- * [B,101,40] model input for 1 s @ 16 kHz, hop 160, n_fft 480, 40 mels/DCT).
+ * pcm [batch][samples] f32 -> out [batch][frames][n_dct] f32 (the [B,101,40] model
+ * input for 1 s @ 16 kHz, hop 160, n_fft 480, 40 mels/DCT), where
+ *   frames = 1 + (samples + 2*(n_fft/2) - n_fft) / hop
+ * is the frame count of the centre-padded clip: 1 + samples/hop for even n_fft; for odd
+ * n_fft the padded clip is one sample shorter, so one frame fewer where hop divides samples.
  * window [n_fft], mel_weights [n_mels][n_fft/2+1], dct [n_dct][n_mels] are the
  * librosa-0.6 Hann window / Slaney mel basis / DCT basis (device, f32).
- * Centre reflect padding, power spectrum, log of positive entries.  batch <= 65535.
+ * Centre reflect padding, power spectrum, log of positive entries.  batch <= 65535;
+ * batch == 0: HONK_OK (for a shape the call takes; the shape is checked first).  HONK_ERR_ARG: a null pointer, batch < 0, samples < 1, n_fft < 2,
+ * hop < 1, n_mels < 1, n_dct < 1, samples <= n_fft/2; HONK_ERR_UNSUPPORTED: n_fft past the
+ * VALU route's LDS plan.
  */
 int honk_mfcc_f32(const float* pcm, int64_t batch, int32_t samples, const float* window, int32_t n_fft,
                   int32_t hop, const float* mel_weights, int32_t n_mels, const float* dct, int32_t n_dct,
                   float* out, void* stream);
+/*
+ * The route honk_mfcc_f32 / honk_pcen_f32 take for a shape (host-only: no GPU work, no
+ * pointer but `plan` dereferenced).  The launches read the very function these report:
+ *   HONK_FRONT_ROUTE_MFMA  frames <= 112, n_fft % 16 == 0, hop % 4 == 0 and the kernel's LDS
+ *                          plan within 160 KiB: one workgroup per clip, the spectrum on the MFMA
+ *   HONK_FRONT_ROUTE_VALU  every other shape (and every shape under HONK_MFCC_VALU=1 in the
+ *                          environment): a direct DFT per (clip, 4 frames), LDS plan within 64 KiB
+ * They return the status and honk_last_error reason the launch would give for the shape:
+ * HONK_ERR_ARG (as above, and a null plan), HONK_ERR_UNSUPPORTED past the VALU route's LDS plan.
+ */
+#define HONK_FRONT_ROUTE_MFMA 1
+#define HONK_FRONT_ROUTE_VALU 2
+typedef struct honk_front_plan_t {
+  int32_t route;     /* HONK_FRONT_ROUTE_*                                                   */
+  int32_t frames;    /* 1 + (samples + 2*(n_fft/2) - n_fft) / hop                            */
+  int32_t n_bins;    /* n_fft/2 + 1                                                          */
+  int32_t launches;  /* kernels per call: 1, or 2 on PCEN's VALU route (energies, then scan) */
+  int64_t lds_bytes; /* dynamic LDS of the main kernel; above 64 KiB the call opts in first  */
+} honk_front_plan_t;
+int honk_mfcc_plan(int32_t samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_dct,
+                   honk_front_plan_t* plan);
+int honk_pcen_plan(int32_t samples, int32_t n_fft, int32_t hop, int32_t n_mels, honk_front_plan_t* plan);
 /*
  * The same front end over a long recording (the /listen serving path, server.py:99-112):
  * every window of `window` samples that starts at sample w * stride of the int16 recording
@@ -377,16 +405,18 @@ int honk_mfcc_windows_i16(const int16_t* pcm_i16, int64_t samples, int32_t windo
  *   E[t][m] = sum_k mel_weights[m][k] * |X_t[k]|^power      power 1 (magnitude) or 2
  *   M[0] = E[0];  M[t] = (1 - s) M[t-1] + s E[t]            per band, reset for every clip
  *   out[t][m] = (E / (M + eps)^alpha + delta)^r - delta^r
- * out [batch][1 + samples/hop][n_mels] f32; no DCT.  The smoother starts at M[0] = E[0]
- * (HONK_PCEN_INIT_FIRST_FRAME, the only initial state built); zero energy gives exactly 0.
+ * out [batch][frames][n_mels] f32 (frames as honk_mfcc_f32's); no DCT.  The smoother starts
+ * at M[0] = E[0] (HONK_PCEN_INIT_FIRST_FRAME, the only initial state built); zero energy
+ * gives exactly 0.
  * params == NULL: the HONK_PCEN_* defaults.  Only enqueues on `stream` (no synchronisation,
- * no allocation, no workspace: capturable); batch <= 65535 per call; batch == 0: HONK_OK.
+ * no allocation, no workspace: capturable); batch <= 65535 per call; batch == 0: HONK_OK
+ * (the shape and the parameters are checked first).
  * One launch when frames <= 112, n_fft % 16 == 0, hop % 4 == 0 and the LDS plan fits (the
  * MFMA MFCC kernel's shapes), else two (mel energies into out, then a segmented scan in
- * place); HONK_MFCC_VALU=1 in the environment forces the latter.  HONK_ERR_ARG: a null
- * pointer, samples <= n_fft/2, s outside (0, 1], eps <= 0, alpha < 0, delta < 0, r <= 0,
- * power not 1 or 2, a non-finite parameter; HONK_ERR_UNSUPPORTED: n_fft past the two-launch
- * route's LDS plan as well.
+ * place); HONK_MFCC_VALU=1 in the environment forces the latter; honk_pcen_plan (above)
+ * reports which.  HONK_ERR_ARG: a null pointer, samples <= n_fft/2, s outside (0, 1],
+ * eps <= 0, alpha < 0, delta < 0, r <= 0, power not 1 or 2, a non-finite parameter;
+ * HONK_ERR_UNSUPPORTED: n_fft past the two-launch route's LDS plan as well.
  */
 #define HONK_PCEN_EPS 1e-6f
 #define HONK_PCEN_S 0.025f

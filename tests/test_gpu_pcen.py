@@ -3,9 +3,11 @@ shared with the MFCC kernel) and the long route (mel energies, then a segmented 
 against the float64 restatement tests/pcen_ref.py, and the callers: compute_pcen_batch,
 DeviceSpeechDataset, train(), TorchLabelService.
 
-PARITY UNPINNED (the reference's ``pcen`` package is absent).  Bound: the project's front-end bound
-(test_gpu_mfcc_matches_oracle), atol = 1e-3 * max(max|ref clip|, 1e-6), rtol = 0 -- the error source
-is the same fp32 spectrum.  Inputs: pcen_ref.clips (speech-like, all-zero, an onset after 8000 zeros,
+PARITY UNPINNED (the reference's ``pcen`` package is absent).  Bound: the front-end bound of
+tests/frontend_geometry_cases.py -- 16 x the error of the float32 restatement oracle/frontend_f32_sim.py
+against the same reference on the same clips, never above 1e-4; atol = bound * max(max|ref clip|, 1e-6),
+rtol = 0, for a device result against the reference and for two device results against each other.
+Inputs: pcen_ref.clips (speech-like, all-zero, an onset after 8000 zeros,
 1e-3 x speech-like)."""
 import os
 import random
@@ -24,13 +26,13 @@ from honk_amd import model as hm
 from honk_amd import service as hs
 from honk_amd import train as htr
 from honk_amd.audio import AudioPreprocessor, mel_filterbank
+from oracle import frontend_f32_sim as sim
 from test_mfcc_windows_abi import _pcm
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEV = "cuda:0"
-REL = 1e-3
 ALT = dict(s=0.1, alpha=0.8, delta=1.0, r=0.25)
 
 
@@ -45,8 +47,14 @@ def _run(ys, **kw):
     return out.cpu().numpy()
 
 
-def _report(name, worst):
-    print(f"pcen {name}: max |err| / max|ref clip| = {worst:.3e} (bound {REL:.0e})")
+def _rel(ys, ref, **kw):
+    """The bound of these clips: kw are pcen()'s keywords (n_fft, n_mels, the PCEN parameters)."""
+    return sim.bound(sim.e32("pcen", ys, ref, **kw))
+
+
+def _report(name, got, ref, rel):
+    worst = pcen_ref.check(got, ref, rel)
+    print(f"pcen {name}: max |err| / max|ref clip| = {worst:.3e} (bound {rel:.1e})")
 
 
 def test_fused_route_matches_reference():
@@ -54,7 +62,7 @@ def test_fused_route_matches_reference():
     ys, ref = pcen_ref.clips(), pcen_ref.ref_clips()
     got = _run(ys)
     assert got.shape == (8, 101, 40)
-    _report("fused S=16000", pcen_ref.check(got, ref, REL))
+    _report("fused S=16000", got, ref, _rel(ys, ref))
     assert np.all(got[pcen_ref.ZERO_CLIP] == 0.0)
 
 
@@ -66,15 +74,16 @@ def test_edge_shapes(S, frames):
     ys, ref = pcen_ref.clips(S), pcen_ref.ref_clips(S)
     got = _run(ys)
     assert got.shape == (8, frames, 40)
-    _report(f"S={S}", pcen_ref.check(got, ref, REL))
+    _report(f"S={S}", got, ref, _rel(ys, ref))
     assert np.all(got[pcen_ref.ZERO_CLIP] == 0.0)
 
 
 def test_twenty_mel_bands():
     _gpu()
-    got = _run(pcen_ref.clips(), n_mels=20)
+    ys, ref = pcen_ref.clips(), pcen_ref.ref_clips(n_mels=20)
+    got = _run(ys, n_mels=20)
     assert got.shape == (8, 101, 20)
-    _report("n_mels=20", pcen_ref.check(got, pcen_ref.ref_clips(n_mels=20), REL))
+    _report("n_mels=20", got, ref, _rel(ys, ref, n_mels=20))
 
 
 @pytest.mark.parametrize("S,frames", [(18080, 114), (48000, 301)])
@@ -84,7 +93,7 @@ def test_long_route_matches_reference(S, frames):
     ys, ref = pcen_ref.clips(S), pcen_ref.ref_clips(S)
     got = _run(ys)
     assert got.shape == (8, frames, 40)
-    _report(f"long S={S}", pcen_ref.check(got, ref, REL))
+    _report(f"long S={S}", got, ref, _rel(ys, ref))
     assert np.all(got[pcen_ref.ZERO_CLIP] == 0.0)
 
 
@@ -94,10 +103,11 @@ def test_long_route_matches_fused_route(monkeypatch):
     fast = _run(ys)
     monkeypatch.setenv("HONK_MFCC_VALU", "1")
     slow = _run(ys)
-    _report("long S=16000", pcen_ref.check(slow, ref, REL))
+    rel = _rel(ys, ref)
+    _report("long S=16000", slow, ref, rel)
     for i in range(len(ys)):
         scale = max(np.abs(ref[i]).max(), 1e-6)
-        np.testing.assert_allclose(slow[i], fast[i], atol=REL * scale, rtol=0)
+        np.testing.assert_allclose(slow[i], fast[i], atol=rel * scale, rtol=0)
     assert np.all(slow[pcen_ref.ZERO_CLIP] == 0.0)
 
 
@@ -105,13 +115,14 @@ def test_long_route_fewer_frames_than_segments(monkeypatch):
     """11 frames on the long route: segments of one frame, 21 of the 32 empty."""
     _gpu()
     monkeypatch.setenv("HONK_MFCC_VALU", "1")
-    got = _run(pcen_ref.clips(1600))
-    _report("long S=1600", pcen_ref.check(got, pcen_ref.ref_clips(1600), REL))
+    ys, ref = pcen_ref.clips(1600), pcen_ref.ref_clips(1600)
+    got = _run(ys)
+    _report("long S=1600", got, ref, _rel(ys, ref))
     assert np.all(got[pcen_ref.ZERO_CLIP] == 0.0)
 
 
 def test_c_abi_n_fft_400():
-    """n_fft = 400 (no multiple of 16: the long route) through the C ABI, params NULL = the defaults."""
+    """n_fft = 400 through the C ABI, params NULL = the defaults."""
     _gpu()
     n_fft, hop, n_mels = 400, 160, 40
     ys, ref = pcen_ref.clips(), pcen_ref.ref_clips(n_fft=n_fft)
@@ -122,7 +133,7 @@ def test_c_abi_n_fft_400():
     rc = _native.load().honk_pcen_f32(pcm.data_ptr(), 8, 16000, win.data_ptr(), n_fft, hop, mel.data_ptr(), n_mels,
                                       None, out.data_ptr(), _native.stream_handle(pcm.device))
     _native.check(rc, "honk_pcen_f32")
-    _report("n_fft=400", pcen_ref.check(out.cpu().numpy(), ref, REL))
+    _report("n_fft=400", out.cpu().numpy(), ref, _rel(ys, ref, n_fft=n_fft))
 
 
 @pytest.mark.parametrize("params", [dict(power=2), ALT], ids=["power2", "alt"])
@@ -133,7 +144,7 @@ def test_parameters(monkeypatch, route, params):
         monkeypatch.setenv("HONK_MFCC_VALU", "1")
     ys, ref = pcen_ref.clips(), pcen_ref.ref_clips(**params)
     got = _run(ys, pcen_params=params)
-    _report(f"{route} {params}", pcen_ref.check(got, ref, REL))
+    _report(f"{route} {params}", got, ref, _rel(ys, ref, **params))
     assert np.all(got[pcen_ref.ZERO_CLIP] == 0.0)
 
 
@@ -155,7 +166,7 @@ def test_capturable():
         assert p.returncode == 0, p.stderr[-3000:]
         z = np.load(out)
         assert z["replay"].shape == (4, 101, 40) and np.array_equal(z["replay"], z["eager"])
-        pcen_ref.check(z["replay"], pcen_ref.ref_clips()[4:8], REL)
+        pcen_ref.check(z["replay"], pcen_ref.ref_clips()[4:8], _rel(pcen_ref.clips()[4:8], pcen_ref.ref_clips()[4:8]))
 
 
 def test_clip_is_independent_of_its_batch():
@@ -163,9 +174,10 @@ def test_clip_is_independent_of_its_batch():
     ys, ref = pcen_ref.clips(), pcen_ref.ref_clips()
     pick = [6, 0, 7]  # the onset clip, a steady one, the quiet one
     small, big = _run(ys[pick]), _run(ys)
+    rel = _rel(ys, ref)
     for j, i in enumerate(pick):
         scale = max(np.abs(ref[i]).max(), 1e-6)
-        np.testing.assert_allclose(small[j], big[i], atol=REL * scale, rtol=0)
+        np.testing.assert_allclose(small[j], big[i], atol=rel * scale, rtol=0)
 
 
 # ---- the data path and train() -------------------------------------------------------------------
