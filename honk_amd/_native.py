@@ -79,6 +79,13 @@ _PROTOS = {
                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.c_void_p]),
     "honk_res_rerun_clips": (ctypes.c_int64, [ctypes.POINTER(ResDesc), ctypes.c_int64]),
+    "honk_res_forward_latency": (ctypes.c_int, [ctypes.POINTER(ResDesc), c_f32p, c_f32p, c_f32p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p]),
+    "honk_res_latency_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ResDesc), ctypes.c_int64]),
+    "honk_res_latency_plan": (ctypes.c_int, [ctypes.POINTER(ResDesc), ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.c_int32]),
     "honk_cnn_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CnnDesc), ctypes.c_int64]),
     "honk_cnn_launch_plan": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "honk_cnn_forward": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.POINTER(ctypes.c_void_p), c_f32p, c_f32p,
@@ -253,7 +260,7 @@ def timing_read():
 
 # HONK_KERNEL_* of include/honk_hip.h
 KERNEL_NAMES = {1: "block_kernel", 2: "block16r_kernel", 3: "block16w_kernel", 4: "block16p_kernel",
-                5: "block16l_kernel"}  # (6 and 7 are retired)
+                5: "block16l_kernel", 8: "block16s_kernel"}  # (6 and 7 are retired)
 
 
 def res_launch_plan(desc, batch: int, n_cus: int = 0):
@@ -265,6 +272,17 @@ def res_launch_plan(desc, batch: int, n_cus: int = 0):
     if n < 0:
         check(n, "honk_res_launch_plan")
     return [KERNEL_NAMES[kinds[i]] for i in range(min(n, 256))]
+
+
+def res_latency_plan(desc, batch: int, n_cus: int = 0):
+    """The block-layer launches honk_res_forward_latency makes per batch chunk:
+    [(kernel name, tiles)].  Host-only."""
+    lib = load()
+    kinds, tiles = (ctypes.c_int32 * 256)(), (ctypes.c_int64 * 256)()
+    n = lib.honk_res_latency_plan(ctypes.byref(desc), int(batch), int(n_cus), kinds, tiles, 256)
+    if n < 0:
+        check(n, "honk_res_latency_plan")
+    return [(KERNEL_NAMES[kinds[i]], int(tiles[i])) for i in range(min(n, 256))]
 
 
 # HONK_CNN_KERNEL_* of include/honk_hip.h (the generic conv GEMM's flags: cnn_kernel_name)

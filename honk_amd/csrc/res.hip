@@ -637,6 +637,7 @@ __global__ __launch_bounds__(256) void tail_sum_live_kernel(const float* __restr
 #include "res_bf16.inc"
 #include "res_bf16r.inc"
 #include "res_bf16w.inc"
+#include "res_bf16s.inc"
 #include "res_bf16p.inc"
 
 // conv0m / conv0p staging: the clip's [Hin][Win] fp32 map through put(r, c, v), 256 threads.
@@ -1441,7 +1442,8 @@ static int max_bands_per_clip(const Layout& L, int TH, int use_dilation) {
 // slowest wave's m-tiles x the MFMA cycles of one m-tile plus a fixed per-tile
 // cost (barrier, first operand reads) -- among the heights whose (TH + 2)-row
 // image (W + d pixels per row + 1) fits the staging buffer.  0: does not fit.
-static int plan_w_th(const Layout& L, int FM, int d) {
+// w_th_max: the tallest of those heights (0: none fits).
+static int w_th_max(const Layout& L, int FM, int d) {
   const int SP = sp_of(FM);
   const int imgpx = g16w_img_px(L.NT, SP);
   const int RW = L.W + d;
@@ -1456,7 +1458,12 @@ static int plan_w_th(const Layout& L, int FM, int d) {
   if ((RW + 1) * CB + 16 * (2 * L.NT) >= 32768) return 0;
   if (0xffffL * 16 - (long)d * RB < (long)L.H * RB) return 0;
   while (thmax >= 1 && ((long)(thmax + 1) * d * RB + RB) / 16 >= 0xffff) --thmax;
+  return thmax < 1 ? 0 : thmax;
+}
+static int plan_w_th(const Layout& L, int FM, int d) {
+  const int thmax = w_th_max(L, FM, d);
   if (thmax < 1) return 0;
+  const int q = L.H / d, rem = L.H - q * d;
   const int ksa = (18 * L.NT + 3) / 4;
   const double c_mt = ksa * L.NT * (FM == 1 ? 3 : FM == 2 ? 2 : 1) * 16.0, c_tile = 1500.0;
   int best = 0;
@@ -1784,6 +1791,36 @@ static int dispatch_block16w(int NT, int FM, const Block16WArgs& a, hipStream_t 
   return fail(HONK_ERR_UNSUPPORTED, "no weight-stationary kernel for NT=%d format %d", NT, FM);
 }
 
+// block16s_kernel: one workgroup per (band tile, out-tile)
+template <int NT, int FM, bool ROWB>
+static int launch_block16s_as(const Block16SArgs& a, int64_t tiles, hipStream_t st) {
+  constexpr int SP = FM == 1 ? 2 : 1;
+  const dim3 gd((unsigned)tiles), bd(G16W<NT, SP, FM>::NTHREADS);
+  const bool vout = a.vout != nullptr, res = a.res != nullptr;
+  if (vout && res) hipLaunchKernelGGL((block16s_kernel<NT, SP, true, true, FM, ROWB>), gd, bd, 0, st, a);
+  else if (vout) hipLaunchKernelGGL((block16s_kernel<NT, SP, true, false, FM, ROWB>), gd, bd, 0, st, a);
+  else if (res) hipLaunchKernelGGL((block16s_kernel<NT, SP, false, true, FM, ROWB>), gd, bd, 0, st, a);
+  else hipLaunchKernelGGL((block16s_kernel<NT, SP, false, false, FM, ROWB>), gd, bd, 0, st, a);
+  HONK_LAUNCH_CHECK("res block16s_kernel");
+  return HONK_OK;
+}
+template <int NT, int FM>
+static int launch_block16s(const Block16SArgs& a, int64_t tiles, hipStream_t st) {
+  if constexpr (FM != 2) {
+    if (a.bias) return launch_block16s_as<NT, FM, true>(a, tiles, st);  // block16r_kernel's arithmetic
+  }
+  return launch_block16s_as<NT, FM, false>(a, tiles, st);
+}
+static int dispatch_block16s(int NT, int FM, const Block16SArgs& a, int64_t tiles, hipStream_t st) {
+#define HONK_S(nt, fm) \
+  if (NT == nt && FM == fm) return launch_block16s<nt, fm>(a, tiles, st);
+  HONK_S(1, 0) HONK_S(2, 0) HONK_S(3, 0)
+  HONK_S(1, 1) HONK_S(2, 1) HONK_S(3, 1)
+  HONK_S(1, 2) HONK_S(2, 2) HONK_S(3, 2)
+#undef HONK_S
+  return fail(HONK_ERR_UNSUPPORTED, "no split band kernel for NT=%d format %d", NT, FM);
+}
+
 template <int NT, int MT, int SP>
 static int launch_block16r(const Block16RArgs& a, hipStream_t st) {
   using G = G16<NT, MT, SP>;
@@ -1934,9 +1971,14 @@ static int launch_conv0_16(const Layout& L, const float* x, void* out, const flo
 struct Step {
   int kind, layer;
   PairPlan pp;  // HONK_KERNEL_PAIR, HONK_KERNEL_LAST
-  int TH;       // HONK_KERNEL_WSTAT, HONK_KERNEL_ROWBAND: the band height and its geometry
+  int TH;       // HONK_KERNEL_WSTAT, HONK_KERNEL_ROWBAND, HONK_KERNEL_SPLIT: the band height and its geometry
   BandGeo bg;
+  bool vout;    // HONK_KERNEL_SPLIT: the last layer, values out (block16s_kernel VOUT)
+  bool rowb;    // HONK_KERNEL_SPLIT: block16r_kernel's arithmetic (block16s_kernel ROWB)
 };
+// how the latency schedule's last layer (a HONK_KERNEL_SPLIT step with vout) gets its channel sums
+// (the layer's own; chsum_stream_kernel; chsum_band_kernel; chsum_rowband_kernel)
+enum LastSums { SUMS_FUSED, SUMS_STREAM, SUMS_BAND, SUMS_ROWBAND };
 struct Schedule {
   int64_t n;  // planned for chunks of n clips on grid workgroups (0: not planned yet)
   int grid;
@@ -1946,6 +1988,9 @@ struct Schedule {
   PlanR pr;          // PATH_ROWBAND: block16r_kernel's
   int parts_last;    // channel-sum partials per clip the last layer leaves the tail
   bool last_stored;  // the last layer ran as a pair's B layer and stored its output (tail_act_kernel)
+  bool latency;      // planned by plan_latency (whether or not it differs from plan_chunk's)
+  LastSums sums;     // latency: who writes the partials
+  Step band_last;    // SUMS_BAND, SUMS_ROWBAND: the throughput schedule's last step (its TH and band geometry)
 };
 // (path = plan_path(L, d, sw): it depends on neither n nor grid, so a call decides it once)
 static Schedule plan_chunk(const Layout& L, const honk_res_desc* d, const Switches& sw, Path path, int64_t n,
@@ -1985,6 +2030,75 @@ static Schedule plan_chunk(const Layout& L, const honk_res_desc* d, const Switch
   return s;
 }
 
+// The latency schedule (honk_res_forward_latency): plan_chunk's, except for a chunk of fewer
+// clips than CUs on the weight-stationary family.  There a workgroup that owns whole clips
+// (the fused pairs, block16l_kernel) or tall bands (plan_w_th) leaves most CUs idle, so every
+// block layer runs as ONE launch of block16s_kernel -- a pair as its two layers -- whose tiles
+// (clip, class, band of TH class rows, out-tile) number at least `cus` where the map has
+// that many: TH = the tallest band that reaches `cus` tiles, 1 where none does.  The last
+// layer writes its values, and the partials the throughput schedule's last kernel would have
+// left are summed from them in its order (sums, band_last), so the tail -- and the logits --
+// are the throughput schedule's bit for bit.  A last layer that plan_chunk stores (bf16, a
+// pair's B layer) is stored here too.  The row-band family runs the same tiles with
+// block16r_kernel's arithmetic (Step::rowb: bias table, residual by selection MFMA, one partial
+// per m-tile) where its maps fit the split kernel's staging image.  f32 and n >= cus:
+// plan_chunk's unchanged.
+constexpr int64_t LAT_MAX_CLIPS = 1024;  // the value buffer (lat_vout_bytes) holds fewer clips than this
+static int lat_th(const Layout& L, int FM, int dl, int64_t n, int cus) {
+  for (int th = w_th_max(L, FM, dl); th > 1; --th)
+    if (n * band_geo(L.H, dl, th).nbc * L.NT >= cus) return th;
+  return 1;
+}
+// (the row-band family too, where every layer's image fits block16s_kernel's staging buffer)
+static bool lat_family(const Layout& L, const honk_res_desc* d, Path path) {
+  if (path == PATH_WSTAT) return true;
+  if (path != PATH_ROWBAND) return false;
+  for (int i = 1; i <= L.L; ++i)
+    if (!w_th_max(L, fmt_of(L.prec), dil_of(d, i))) return false;
+  return L.L >= 1;
+}
+static bool lat_applies(const Layout& L, const honk_res_desc* d, Path path, int64_t n, int cus) {
+  return lat_family(L, d, path) && n < cus && n < LAT_MAX_CLIPS;
+}
+static Schedule plan_latency(const Layout& L, const honk_res_desc* d, const Switches& sw, Path path, int64_t n,
+                             int cus) {
+  const Schedule def = plan_chunk(L, d, sw, path, n, cus > n ? (int)n : cus);
+  Schedule s = def;
+  s.latency = true;
+  if (!lat_applies(L, d, path, n, cus)) return s;
+  const int FM = fmt_of(L.prec);
+  s.steps.clear();
+  auto split = [&](int i, bool vout) {
+    const int dl = dil_of(d, i), th = lat_th(L, FM, dl, n, cus);
+    Step st{HONK_KERNEL_SPLIT, i, PairPlan{}, th, band_geo(L.H, dl, th)};
+    st.vout = vout;
+    st.rowb = path == PATH_ROWBAND;
+    s.steps.push_back(st);
+  };
+  for (const Step& t : def.steps) {
+    if (t.kind == HONK_KERNEL_ROWBAND) {
+      split(t.layer, t.layer == L.L);
+      if (t.layer == L.L) {
+        s.sums = SUMS_ROWBAND;
+        s.band_last = t;
+      }
+    } else if (t.kind == HONK_KERNEL_PAIR) {
+      split(t.layer, false);
+      split(t.layer + 1, false);
+    } else if (t.kind == HONK_KERNEL_LAST) {
+      split(t.layer, true);
+      s.sums = SUMS_STREAM;
+    } else if (t.layer == L.L) {  // HONK_KERNEL_WSTAT, the last layer
+      split(t.layer, true);
+      s.sums = SUMS_BAND;
+      s.band_last = t;
+    } else {
+      split(t.layer, false);
+    }
+  }
+  return s;
+}
+
 // res_vf.hip (compiled with its own flags): the pair and last-layer launches
 bool launch_pair_vf(int FM, int ppr, bool imm, int dA, int dB, dim3 gd, dim3 bd, hipStream_t st,
                     const Block16PArgs& pa);
@@ -2008,6 +2122,7 @@ struct Chunk16 {
   LiveRef live;
   int64_t n;  // the chunk's clips, on grid workgroups
   int grid;
+  float* vout;  // the latency schedule's value buffer (lat_vout_bytes), else null
   double layer_flop() const { return 2.0 * L.H * L.W * L.C * L.C * 9 * (double)n; }
 };
 
@@ -2092,6 +2207,73 @@ static int run_wstat(const Chunk16& c, const Step& s) {
   tl.done(c.st);
   return rc;
 }
+static int run_split(const Chunk16& c, const Step& s) {
+  const Layout& L = c.L;
+  const bool even = (s.layer % 2) == 0;
+  if (s.vout && !c.vout) return fail(HONK_ERR_ARG, "latency schedule without its value buffer");
+  Block16SArgs a;
+  a.in = even ? c.X : c.R;
+  a.res = even ? c.R : nullptr;
+  a.out = s.vout ? nullptr : (even ? c.R : c.X);
+  a.vout = s.vout ? c.vout : nullptr;
+  a.bias = s.rowb ? c.packed + L.off_bias16 + (size_t)16 * L.CP * (s.layer - 1) : nullptr;
+  a.wfrag = (const char*)(c.frb + (size_t)(s.layer - 1) * c.frl);
+  a.H = L.H;
+  a.W = L.W;
+  a.dil = dil_of(c.d, s.layer);
+  a.lgd = 0;
+  while ((1 << a.lgd) < a.dil) ++a.lgd;
+  a.TH = s.TH;
+  a.nclips = (int)c.n;
+  a.rem = s.bg.rem;
+  a.nb1 = s.bg.nb1;
+  a.nb0 = s.bg.nb0;
+  a.nbc = s.bg.nbc;
+  a.live = c.live;
+  const int64_t tiles = c.n * s.bg.nbc * L.NT;
+  if (tiles > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
+  TimedLaunch tl(c.st, c.layer_flop());
+  const int rc = dispatch_block16s(L.NT, c.FM, a, tiles, c.st);
+  tl.done(c.st);
+  return rc;
+}
+// the last layer's partials from the values run_split left (Schedule::sums)
+static int run_last_sums(const Chunk16& c, const Schedule& s) {
+  const Layout& L = c.L;
+  const int dl = dil_of(c.d, L.L);
+  int lgd = 0;
+  while ((1 << lgd) < dl) ++lgd;
+  if (s.sums == SUMS_STREAM) {
+#define HONK_CS(nt)                                                                                         \
+  if (L.NT == nt)                                                                                           \
+    hipLaunchKernelGGL(chsum_stream_kernel<nt>, dim3((unsigned)c.n), dim3(128), 0, c.st, (const float*)c.vout, \
+                       c.chsum, L.H, L.W, dl, lgd, c.live);
+    HONK_CS(1) HONK_CS(2) HONK_CS(3)
+#undef HONK_CS
+    HONK_LAUNCH_CHECK("res chsum_stream_kernel");
+  } else if (s.sums == SUMS_BAND) {
+    const BandGeo& bg = s.band_last.bg;
+#define HONK_CB(nt)                                                                                          \
+  if (L.NT == nt)                                                                                            \
+    hipLaunchKernelGGL(chsum_band_kernel<nt>, dim3((unsigned)(c.n * bg.nbc)), dim3(256), 0, c.st,            \
+                       (const float*)c.vout, c.chsum, L.H, L.W, dl, lgd, s.band_last.TH, bg.rem, bg.nb1, bg.nb0, \
+                       bg.nbc, (int)c.n, c.live);
+    HONK_CB(1) HONK_CB(2) HONK_CB(3)
+#undef HONK_CB
+    HONK_LAUNCH_CHECK("res chsum_band_kernel");
+  } else if (s.sums == SUMS_ROWBAND) {
+    const BandGeo& bg = s.band_last.bg;
+#define HONK_CR(nt)                                                                                          \
+  if (L.NT == nt)                                                                                            \
+    hipLaunchKernelGGL(chsum_rowband_kernel<nt>, dim3((unsigned)(c.n * bg.nbc)), dim3(256), 0, c.st,         \
+                       (const float*)c.vout, c.chsum, L.H, L.W, dl, s.band_last.TH, s.pr.MT, bg.rem, bg.nb1, bg.nb0, \
+                       bg.nbc, (int)c.n, c.live);
+    HONK_CR(1) HONK_CR(2) HONK_CR(3)
+#undef HONK_CR
+    HONK_LAUNCH_CHECK("res chsum_rowband_kernel");
+  }
+  return HONK_OK;
+}
 static int run_rowband(const Chunk16& c, const Step& s, const PlanR& pr) {
   Block16RArgs a;
   int rc = fill_band(c, s, &a);
@@ -2139,7 +2321,7 @@ static int run_tail16(const Chunk16& c, const Schedule& s, float* logits, const 
 static int forward_bf16(const Layout& L, const honk_res_desc* d, const Switches& sw, Schedule* sch,
                         const float* packed, const float* x, float* logits, int64_t batch, int64_t chunk,
                         void* workspace, hipStream_t st, int* flags = nullptr,
-                        LiveRef live = LiveRef{nullptr, 0, 0}) {
+                        LiveRef live = LiveRef{nullptr, 0, 0}, float* vout = nullptr) {
   const int FM = fmt_of(L.prec), SP = sp_of(FM);
   if (live.count && (FM != 1 || batch > chunk))
     return fail(HONK_ERR_UNSUPPORTED, "a device-held clip count: bf16x3, one chunk");
@@ -2150,7 +2332,7 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const Switches&
   const float* tail_cs = FM == 2 ? cscale : nullptr;
   Chunk16 c{L, d, packed, FM, SP, R, R + act, cscale + round64((size_t)chunk),
             FM == 1 ? packed + L.off_fragx3 : FM == 2 ? packed + L.off_fragh : packed + L.off_frag16,
-            FM == 0 ? L.frag16_floats : L.fragx3_floats, st, live, 0, 0};
+            FM == 0 ? L.frag16_floats : L.fragx3_floats, st, live, 0, 0, vout};
   const float* w0 = packed + L.off_conv0;
   const Path path = sch->n ? sch->path : plan_path(L, d, sw);
   if (path != PATH_WSTAT && path != PATH_ROWBAND) return refuse_path(L, path);
@@ -2175,13 +2357,18 @@ static int forward_bf16(const Layout& L, const honk_res_desc* d, const Switches&
                    : launch_conv0_16<0, false>(L, xc, R, w0, c.n, st, nullptr, live, sw.conv0);
     if (rc) return rc;
     // (planned with conv0 enqueued: a small batch's planning runs under it, not ahead of the first launch)
-    if (sch->n != c.n || sch->grid != c.grid) *sch = plan_chunk(L, d, sw, path, c.n, c.grid);
+    // (vout: the latency schedule, honk_res_forward_latency)
+    if (sch->n != c.n || sch->grid != c.grid || sch->latency != (vout != nullptr))
+      *sch = vout ? plan_latency(L, d, sw, path, c.n, cu_count()) : plan_chunk(L, d, sw, path, c.n, c.grid);
     for (const Step& s : sch->steps) {
       rc = s.kind == HONK_KERNEL_WSTAT     ? run_wstat(c, s)
            : s.kind == HONK_KERNEL_ROWBAND ? run_rowband(c, s, sch->pr)
+           : s.kind == HONK_KERNEL_SPLIT   ? run_split(c, s)
                                            : run_pair(c, s);
       if (rc) return rc;
     }
+    rc = run_last_sums(c, *sch);
+    if (rc) return rc;
     rc = run_tail16(c, *sch, logits + c0 * L.NL, tail_cs, flags ? flags + c0 : nullptr);
     if (rc) return rc;
   }
@@ -2306,6 +2493,19 @@ static size_t ws_need(const honk_res_desc* d, const Switches& sw, int64_t batch)
   }
   return ws_bytes_plain(d, sw, batch);
 }
+
+// The latency schedule's workspace: ws_need's, rounded up to 256 B, then the last layer's
+// fp32 values [clips][H][W][CP] (block16s_kernel VOUT) for as many clips of a chunk as the
+// schedule can apply to (plan_latency).  Host-only: the bound is LAT_MAX_CLIPS, not a CU count.
+static size_t lat_vout_bytes(const honk_res_desc* d, const Switches& sw, int64_t batch) {
+  Layout L;
+  if (make_layout(d, &L) != HONK_OK || batch < 1 || L.prec == HONK_PREC_F32) return 0;
+  if (!lat_family(L, d, plan_path(L, d, sw))) return 0;
+  const int64_t ch = chunk_clips(L, sw, batch);
+  const int64_t n = ch < LAT_MAX_CLIPS - 1 ? ch : LAT_MAX_CLIPS - 1;
+  return ((size_t)n * L.H * L.W * L.CP * sizeof(float) + 255) & ~(size_t)255;
+}
+static size_t lat_ws_main(size_t need) { return (need + 255) & ~(size_t)255; }
 
 static thread_local int64_t g_rerun = 0;
 
@@ -2463,7 +2663,7 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
 // cap keep their f16x2 logits.
 static int rerun_flagged(const Layout& L, const honk_res_desc* d, const Switches& sw, const F16Check& p,
                          const float* packed, const float* x, float* logits, void* workspace, int64_t bound,
-                         LiveRef live, hipStream_t st) {
+                         LiveRef live, hipStream_t st, float* vout = nullptr) {
   const honk_res_desc e = rerun_desc(d);
   Layout L3;
   int rc = make_layout(&e, &L3);
@@ -2478,7 +2678,7 @@ static int rerun_flagged(const Layout& L, const honk_res_desc* d, const Switches
     const LiveRef lv{live.count, live.cap, live.count ? (int)o : 0};
     hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)n), dim3(256), 0, st, x, list + o, L.Hin * L.Win, gx, lv);
     HONK_LAUNCH_CHECK("res gather_clips_kernel");
-    rc = forward_bf16(L3, &e, sw, &sch, packed, gx, glog, n, chunk_clips(L3, sw, n), workspace, st, nullptr, lv);
+    rc = forward_bf16(L3, &e, sw, &sch, packed, gx, glog, n, chunk_clips(L3, sw, n), workspace, st, nullptr, lv, vout);
     if (rc) return rc;
     hipLaunchKernelGGL(scatter_logits_kernel, dim3((unsigned)cdiv(n * L.NL, 64)), dim3(64), 0, st, glog, list + o,
                        (int)n, L.NL, logits, lv);
@@ -2488,10 +2688,12 @@ static int rerun_flagged(const Layout& L, const honk_res_desc* d, const Switches
 }
 
 // honk_res_forward (ordered = false) and honk_res_forward_ordered (true: no host read of
-// the flagged-clip count -- cap and flagged_out are its arguments)
+// the flagged-clip count -- cap and flagged_out are its arguments); latency (with ordered):
+// honk_res_forward_latency -- the 16-bit chunks planned by plan_latency, the workspace with its
+// value buffer behind ws_need's
 static int res_forward(const honk_res_desc* d, const float* packed, const float* x, float* logits, int64_t batch,
                        void* workspace, size_t ws_bytes, void* stream, bool ordered, int64_t cap,
-                       int32_t* flagged_out) {
+                       int32_t* flagged_out, bool latency = false) {
   Layout L;
   int rc = make_layout(d, &L);
   if (rc) return rc;
@@ -2507,9 +2709,14 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
   }
   if (!packed || !x || !logits || !workspace) return fail(HONK_ERR_ARG, "null pointer argument");
   const Switches sw = read_switches();
-  const size_t need = ws_need(d, sw, batch);
+  size_t need = ws_need(d, sw, batch);
   // (the ordered entry enqueues nothing for a shape the kernels do not take: the reason is set)
   if (ordered && need == 0) return HONK_ERR_UNSUPPORTED;
+  float* vout = nullptr;
+  if (latency && L.prec != HONK_PREC_F32) {
+    vout = (float*)((char*)workspace + lat_ws_main(need));
+    need = lat_ws_main(need) + lat_vout_bytes(d, sw, batch);
+  }
   if (ws_bytes < need)
     return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
@@ -2528,7 +2735,7 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
     char* ws = (char*)workspace;
     int* flags = (int*)(ws + p.flags);
     int* count = (int*)(ws + p.count);
-    rc = forward_bf16(L, d, sw, &sch, packed, x, logits, batch, chunk, workspace, st, flags);
+    rc = forward_bf16(L, d, sw, &sch, packed, x, logits, batch, chunk, workspace, st, flags, LiveRef{nullptr, 0, 0}, vout);
     if (rc) return rc;
     hipLaunchKernelGGL(flag_compact_kernel, dim3(1), dim3(1024), 0, st, flags, batch, (int*)(ws + p.list), count);
     HONK_LAUNCH_CHECK("res flag_compact_kernel");
@@ -2538,7 +2745,7 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
         HONK_LAUNCH_CHECK("res count_out_kernel");
       }
       if (cap <= 0 || cap > batch) cap = batch;
-      return rerun_flagged(L, d, sw, p, packed, x, logits, workspace, cap, LiveRef{count, (int)cap, 0}, st);
+      return rerun_flagged(L, d, sw, p, packed, x, logits, workspace, cap, LiveRef{count, (int)cap, 0}, st, vout);
     }
     int flagged = 0;
     HONK_HIP_CHECK(hipMemcpyAsync(&flagged, count, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2546,7 +2753,9 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
     g_rerun = flagged;
     return rerun_flagged(L, d, sw, p, packed, x, logits, workspace, flagged, LiveRef{nullptr, 0, 0}, st);
   }
-  if (L.prec != HONK_PREC_F32) return forward_bf16(L, d, sw, &sch, packed, x, logits, batch, chunk, workspace, st);
+  if (L.prec != HONK_PREC_F32)
+    return forward_bf16(L, d, sw, &sch, packed, x, logits, batch, chunk, workspace, st, nullptr, LiveRef{nullptr, 0, 0},
+                        vout);
   const size_t act = (size_t)chunk * L.H * L.W * L.CP;
   float* R = (float*)workspace;
   float* X[2] = {R + act, R + 2 * act};
@@ -2611,6 +2820,46 @@ int honk_res_forward_ordered(const honk_res_desc* d, const float* packed, const 
                              int64_t batch, void* workspace, size_t ws_bytes, void* stream,
                              int64_t rerun_capacity, int32_t* flagged_count) {
   return res_forward(d, packed, x, logits, batch, workspace, ws_bytes, stream, true, rerun_capacity, flagged_count);
+}
+
+int honk_res_forward_latency(const honk_res_desc* d, const float* packed, const float* x, float* logits,
+                             int64_t batch, void* workspace, size_t ws_bytes, void* stream,
+                             int64_t rerun_capacity, int32_t* flagged_count) {
+  return res_forward(d, packed, x, logits, batch, workspace, ws_bytes, stream, true, rerun_capacity, flagged_count,
+                     true);
+}
+
+size_t honk_res_latency_workspace_bytes(const honk_res_desc* d, int64_t batch) {
+  const Switches sw = read_switches();
+  const size_t need = ws_need(d, sw, batch);
+  if (need == 0 || d->precision == HONK_PREC_F32) return need;
+  return lat_ws_main(need) + lat_vout_bytes(d, sw, batch);
+}
+
+int honk_res_latency_plan(const honk_res_desc* d, int64_t batch, int32_t n_cus, int32_t* kinds, int64_t* tiles,
+                          int32_t max_steps) {
+  Layout L;
+  int rc = make_layout(d, &L);
+  if (rc) return rc;
+  if (batch < 1) return fail(HONK_ERR_ARG, "batch < 1");
+  const Switches sw = read_switches();
+  const int64_t n = chunk_clips(L, sw, batch);
+  const int cus = n_cus > 0 ? n_cus : cu_count();
+  const Schedule s = plan_latency(L, d, sw, plan_path(L, d, sw), n, cus);
+  if (s.path == PATH_NO_WIDTH) return fail(HONK_ERR_UNSUPPORTED, "width beyond the row-band staging plan");
+  if (s.path == PATH_NO_F16X2)
+    return fail(HONK_ERR_UNSUPPORTED, "f16x2: outside the weight-stationary / pair kernels' envelope");
+  const int cnt = (int)s.steps.size();
+  for (int k = 0; k < cnt && k < max_steps; ++k) {
+    const Step& t = s.steps[k];
+    if (kinds) kinds[k] = t.kind;
+    if (tiles)
+      tiles[k] = t.kind == HONK_KERNEL_SPLIT       ? n * t.bg.nbc * L.NT
+                 : t.kind == HONK_KERNEL_BLOCK_F32 ? n * s.p32.nbands
+                 : t.kind == HONK_KERNEL_PAIR || t.kind == HONK_KERNEL_LAST ? (int64_t)s.grid
+                                                                            : n * t.bg.nbc;
+  }
+  return cnt;
 }
 
 int64_t honk_res_rerun_clips(const honk_res_desc* d, int64_t batch) {

@@ -224,6 +224,11 @@ class SpeechResModel(SerializableModule):
         self.honk_stream_ordered = False
         self.honk_rerun_capacity = None
         self.honk_last_rerun_dev = None
+        # "throughput": the schedule planned for large batches (a workgroup owns whole clips or
+        # tall row bands).  "latency": honk_res_forward_latency -- batches of fewer clips than the
+        # device has CUs run every block layer split over all CUs (the same logits bit for bit;
+        # larger batches run the throughput schedule); implies the stream-ordered contract above.
+        self.honk_schedule = "throughput"
 
     # -- reference forward (CPU tensors / training mode): model.py:104-121 --
     # native_convs: training on a ROCm tensor runs the stem (conv0 + relu + pool) on
@@ -425,23 +430,28 @@ class SpeechResModel(SerializableModule):
             self.honk_last_precision = precision or self.honk_precision
             B = x.shape[0]
             out = torch.empty(B, self._honk_desc["n_labels"], dtype=torch.float32, device=x.device)
-            ordered = self.honk_stream_ordered
+            if self.honk_schedule not in ("throughput", "latency"):
+                raise ValueError("honk_schedule must be 'throughput' or 'latency'")
+            latency = self.honk_schedule == "latency"
+            ordered = self.honk_stream_ordered or latency
             if ordered:
                 self.honk_last_rerun = None
                 self.honk_last_rerun_dev = torch.zeros((), dtype=torch.int32, device=x.device)
             if B == 0:
                 return out
-            ws_bytes = lib.honk_res_workspace_bytes(desc, B)
+            ws_query = "honk_res_latency_workspace_bytes" if latency else "honk_res_workspace_bytes"
+            ws_bytes = getattr(lib, ws_query)(desc, B)
             if ws_bytes == 0:
-                _native.check(-1, "honk_res_workspace_bytes")
+                _native.check(-1, ws_query)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
             if ordered:
                 cap = self.honk_rerun_capacity
-                _native.check(lib.honk_res_forward_ordered(desc, packed.data_ptr(), x.data_ptr(), out.data_ptr(), B,
-                                                           ws.data_ptr(), ws_bytes, _native.stream_handle(x.device),
-                                                           0 if cap is None else int(cap),
-                                                           self.honk_last_rerun_dev.data_ptr()),
-                              "honk_res_forward_ordered")
+                entry = "honk_res_forward_latency" if latency else "honk_res_forward_ordered"
+                _native.check(getattr(lib, entry)(desc, packed.data_ptr(), x.data_ptr(), out.data_ptr(), B,
+                                                  ws.data_ptr(), ws_bytes, _native.stream_handle(x.device),
+                                                  0 if cap is None else int(cap),
+                                                  self.honk_last_rerun_dev.data_ptr()),
+                              entry)
                 return out
             _native.check(lib.honk_res_forward(desc, packed.data_ptr(), x.data_ptr(), out.data_ptr(), B,
                                                ws.data_ptr(), ws_bytes, _native.stream_handle(x.device)),
@@ -458,10 +468,11 @@ class SpeechResModel(SerializableModule):
         One eager forward runs first: the once-per-pack synchronisations (weight pack,
         numerics record, the precision policy's probe, the CU-count query) happen there,
         outside the capture.  The capture itself is the launches of
-        ``honk_res_forward_ordered`` on the capture stream, with ``honk_rerun_capacity`` as it
-        is now; the flagged-clip count is read by the kernels at every replay, so one graph
-        serves batches with any number of out-of-calibration clips.  A later change of the
-        weights, ``honk_precision`` or ``honk_rerun_capacity`` needs a new capture."""
+        ``honk_res_forward_ordered`` (``honk_schedule = "latency"``: ``honk_res_forward_latency``)
+        on the capture stream, with ``honk_rerun_capacity`` as it is now; the flagged-clip count
+        is read by the kernels at every replay, so one graph serves batches with any number of
+        out-of-calibration clips.  A later change of the weights, ``honk_precision``,
+        ``honk_schedule`` or ``honk_rerun_capacity`` needs a new capture."""
         if self.training:
             raise RuntimeError("honk_capture needs eval mode (module.eval())")
         if not (torch.is_tensor(x_example) and x_example.is_cuda and x_example.dim() == 3

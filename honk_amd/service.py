@@ -56,18 +56,25 @@ class TorchLabelService(LabelService):
     (``SpeechResModel.honk_capture``, captured at the first call) instead of launching the
     forward's kernels one by one; ``reload()`` drops the capture.
 
+    ``honk_latency`` (opt-in, default False): with a ``SpeechResModel`` as ``self.model``, ``label()``,
+    ``label_batch()``, ``label_stream()`` (and a ``StreamListener`` on this service) run the model's
+    latency schedule (``SpeechResModel.honk_schedule = "latency"``: a small batch split over all
+    CUs, the same logits); with ``honk_graph``, ``label()`` replays a capture of that schedule.
+
     ``audio_preprocess_type`` ("MFCCs", the default, or "PCEN"): the front end the checkpoint was
     trained with (the reference's ``--audio_preprocess_type``).  PCEN restarts its smoother for every
     window, as the reference's ``compute_pcen`` resets its transform after every clip."""
 
     honk_graph = False
+    honk_latency = False
 
     def __init__(self, model_filename, no_cuda=False, labels=["_silence_", "_unknown_", "command", "random"],
-                 audio_processor=None, honk_graph=False, audio_preprocess_type="MFCCs"):
+                 audio_processor=None, honk_graph=False, audio_preprocess_type="MFCCs", honk_latency=False):
         if audio_preprocess_type not in ("MFCCs", "PCEN"):
             raise ValueError(f"TorchLabelService: audio_preprocess_type {audio_preprocess_type!r}")
         self.audio_preprocess_type = audio_preprocess_type
         self.honk_graph = honk_graph
+        self.honk_latency = honk_latency
         self.labels = labels
         self.model_filename = model_filename
         self.no_cuda = no_cuda
@@ -97,9 +104,17 @@ class TorchLabelService(LabelService):
             return torch.from_numpy(np.stack([self.audio_processor.compute_mfccs(p).squeeze(2) for p in pcm]))
         return self.audio_processor.compute_mfccs_batch(torch.from_numpy(pcm).cuda())
 
+    def _net(self):
+        """self.model, on the latency schedule where honk_latency asks for it."""
+        m = self.model
+        if self.honk_latency and isinstance(m, model.SpeechResModel) and m.honk_schedule != "latency":
+            m.honk_schedule = "latency"
+            self._honk_captured = None  # (a capture holds the schedule it was made with)
+        return m
+
     def _forward1(self, model_in):
         """The model's forward of label()'s batch-1 input: the captured one where honk_graph asks for it."""
-        m = self.model
+        m = self._net()
         if not (self.honk_graph and isinstance(m, model.SpeechResModel) and model_in.is_cuda and not m.training):
             return m(model_in)
         cap = getattr(self, "_honk_captured", None)
@@ -119,7 +134,7 @@ class TorchLabelService(LabelService):
         if not windows:
             return []
         with torch.no_grad():
-            p = F.softmax(self.model(self._model_input(windows)).cpu(), dim=1).numpy()
+            p = F.softmax(self._net()(self._model_input(windows)).cpu(), dim=1).numpy()
         return [(self.labels[int(np.argmax(r))], float(np.max(r))) for r in p]
 
     def listen(self, wav_data, stride_size_ms=500, method="labels", keyword="command", min_keyword_prob=0.85):
@@ -165,7 +180,7 @@ class TorchLabelService(LabelService):
                     x = self.audio_processor.compute_pcen_batch(pcmf[w0:w0 + nw].contiguous())
                 else:
                     x = self.audio_processor.compute_mfccs_windows(pcm, stride_bytes // 2, 16000, w0, nw)
-                p = F.softmax(self.model(x).cpu(), dim=1).numpy()
+                p = F.softmax(self._net()(x).cpu(), dim=1).numpy()
                 out.extend((self.labels[int(np.argmax(r))], float(np.max(r))) for r in p)
         return out
 

@@ -207,6 +207,36 @@ int honk_res_forward_ordered(const honk_res_desc* d, const float* packed, const 
 /* Host-only: the clips one bf16x3 re-run round of the f16x2 admission takes for `batch`
    clips (both entry points), or 0: not F16X2, the admission off, or an unsupported shape. */
 int64_t honk_res_rerun_clips(const honk_res_desc* d, int64_t batch);
+/*
+ * The LATENCY schedule of the same forward, for batches smaller than the device's CU count.
+ * The schedule above is planned for throughput: on the 16-bit paths a workgroup owns whole
+ * clips (the fused pairs, the last-layer kernel) or tall row bands, so a batch of B clips
+ * keeps B of the CUs busy and its latency does not fall with B.  Here every block layer of a
+ * chunk of fewer clips than CUs (and fewer than 1024) in BF16 / BF16X3 / F16X2 is one launch of
+ * the split band kernel (HONK_KERNEL_SPLIT): tiles of (clip, dilation class, band of class
+ * rows, 16 out channels), at least one per CU where the map has that many.  Per output the
+ * arithmetic and its order are those of the kernel the throughput schedule runs (the
+ * weight-stationary / pair kernels', or the row-band kernel's), and the last layer's channel
+ * sums are added in its order: the logits are BIT FOR BIT honk_res_forward_ordered's.  Chunks
+ * of at least as many clips as CUs and F32 run the throughput schedule unchanged (as does a
+ * row-band map too wide for the split kernel's staging image).
+ *
+ * honk_res_forward_latency: honk_res_forward_ordered's contract in every respect (enqueue
+ * only, capturable, status codes, batch == 0, rerun_capacity, flagged_count; the re-run
+ * rounds run in this schedule too) with the workspace of honk_res_latency_workspace_bytes.
+ * honk_res_latency_plan: the block-layer launches of one chunk -- kinds[i] = HONK_KERNEL_*,
+ * tiles[i] = the launch's tiles (workgroups' worth of work: band tiles x out-tiles for
+ * HONK_KERNEL_SPLIT, bands for the band kernels, workgroups for the pair / last kernels); either
+ * may be NULL; up to max_steps written.  Returns the launch count or a (negative) HONK_ERR_*
+ * code, refusing what honk_res_launch_plan refuses.  Both queries are host-only.
+ */
+#define HONK_KERNEL_SPLIT 8     /* one layer, split over all CUs (block16s_kernel)         */
+int honk_res_forward_latency(const honk_res_desc* d, const float* packed, const float* x, float* logits,
+                             int64_t batch, void* workspace, size_t workspace_bytes, void* stream,
+                             int64_t rerun_capacity, int32_t* flagged_count /* device, may be NULL */);
+size_t honk_res_latency_workspace_bytes(const honk_res_desc* d, int64_t batch);
+int honk_res_latency_plan(const honk_res_desc* d, int64_t batch, int32_t n_cus, int32_t* kinds, int64_t* tiles,
+                          int32_t max_steps);
 
 /* ---- SpeechModel (cnn-*); utils/model.py:123-205 ------------------------------ */
 typedef struct honk_cnn_desc {
