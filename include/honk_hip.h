@@ -28,6 +28,22 @@
  * as bf16 hi + lo pairs, 3 bf16 MFMA products per MAC, fp32 accumulation -- both
  * meet the 1e-4 logit bar; HONK_PREC_BF16: bf16, top-1 parity); every other
  * entry point is IEEE fp32 (MFMA / FMA), the BatchNorm statistics fp64.
+ * Memory contract, one sentence per buffer class ("Memory contract";
+ * enforced by tests/test_gpu_memory_contract.py on poisoned, guard-banded buffers):
+ *  - workspace: its contents on entry are ignored (every region is written by a
+ *    launch of the same call before a launch of that call reads it, indices and
+ *    counts included), only bytes [0, *_workspace_bytes) are touched, and what it
+ *    holds on return is unspecified.
+ *  - outputs (logits, out, y, dx, dw, db, mean, invstd, masks, loss, flagged_count):
+ *    contents on entry are ignored and every element of the documented shape is
+ *    written, nothing before or behind it.
+ *  - packed: honk_res_pack ignores its contents on entry and writes every float a
+ *    forward or honk_res_numerics reads, within [0, honk_res_packed_floats); the
+ *    pad floats between its regions stay as they were and are never read.
+ *  - inputs (x, pcm, packed in a forward, tensors[i], weights, labels, saved
+ *    activations): never modified.
+ *  - in-place buffers (honk_sgd_step_f32's params and momentum_buf, the running
+ *    statistics): elements [0, n) are read and written, nothing outside them.
  */
 #ifndef HONK_HIP_H
 #define HONK_HIP_H
