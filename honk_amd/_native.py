@@ -90,6 +90,22 @@ _PROTOS = {
     "honk_cnn_launch_plan": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "honk_cnn_forward": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.POINTER(ctypes.c_void_p), c_f32p, c_f32p,
                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "honk_cnn_forward_latency": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.POINTER(ctypes.c_void_p), c_f32p,
+                                                c_f32p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+                                                ctypes.c_void_p]),
+    "honk_cnn_latency_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CnnDesc), ctypes.c_int64]),
+    "honk_cnn_latency_plan": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.c_int32]),
+    "honk_cnn_latency_threshold": (ctypes.c_int64, [ctypes.POINTER(CnnDesc), ctypes.c_int32]),
+    "honk_cnn_features_f32": (ctypes.c_int, [ctypes.POINTER(CnnDesc), ctypes.POINTER(ctypes.c_void_p), c_f32p, c_f32p,
+                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                             ctypes.c_int32]),
+    "honk_linear_splitk_slices": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),
+    "honk_linear_splitk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "honk_linear_splitk_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.c_void_p]),
     "honk_conv2d_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int64] + [ctypes.c_int32] * 9
                         + [ctypes.c_void_p]),
     "honk_maxpool2d_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64] + [ctypes.c_int32] * 5
@@ -289,8 +305,14 @@ def res_latency_plan(desc, batch: int, n_cus: int = 0):
 CNN_KERNEL_NAMES = {1: "conv1x3_kernel", 2: "conv1f_kernel", 3: "conv2x3_kernel", 4: "conv2f_kernel",
                     5: "maxpool_kernel", 6: "pack_conv2x3_kernel", 7: "pack_conv2f_kernel",
                     8: "linear_small_kernel<4>", 9: "linear_small_kernel<8>", 10: "linear_small_kernel<16>",
-                    11: "linear_gemm<f32>", 12: "linear_gemm<x3>"}
+                    11: "linear_gemm<f32>", 12: "linear_gemm<x3>",
+                    # the latency schedule's (honk_cnn_latency_plan)
+                    13: "conv1xs_kernel", 14: "conv1fs_kernel", 15: "conv2xs_kernel", 32: "conv2fs_kernel",
+                    33: "linear_splitk_kernel", 34: "linear_splitk_sum_kernel"}
 CNN_KERNEL_GEMM = 16
+# a dedicated conv of the throughput plan -> its split form in the latency plan
+CNN_SPLIT_OF = {"conv1x3_kernel": "conv1xs_kernel", "conv1f_kernel": "conv1fs_kernel",
+                "conv2x3_kernel": "conv2xs_kernel", "conv2f_kernel": "conv2fs_kernel"}
 
 
 def cnn_kernel_name(kind: int) -> str:
@@ -314,6 +336,26 @@ def cnn_launch_plan(desc):
     if n < 0:
         check(n, "honk_cnn_launch_plan")
     return [cnn_kernel_name(kinds[i]) for i in range(min(n, 16))]
+
+
+def cnn_latency_plan(desc, batch: int, n_cus: int = 0):
+    """The launches honk_cnn_forward_latency makes for one chunk of ``batch`` clips on a device
+    of ``n_cus`` CUs (0: ask the device): [(kernel name, workgroups)], under the current
+    HONK_CNN_* environment.  Host-only where n_cus > 0."""
+    kinds, tiles = (ctypes.c_int32 * 16)(), (ctypes.c_int64 * 16)()
+    n = load().honk_cnn_latency_plan(ctypes.byref(desc), int(batch), int(n_cus), kinds, tiles, 16)
+    if n < 0:
+        check(n, "honk_cnn_latency_plan")
+    return [(cnn_kernel_name(kinds[i]), int(tiles[i])) for i in range(min(n, 16))]
+
+
+def cnn_latency_threshold(desc, n_cus: int = 0) -> int:
+    """Chunks of fewer clips than this run the latency schedule's split kernels in the descriptor's
+    precision (n_cus 0: ask the device)."""
+    n = load().honk_cnn_latency_threshold(ctypes.byref(desc), int(n_cus))
+    if n < 0:
+        check(int(n), "honk_cnn_latency_threshold")
+    return int(n)
 
 
 def front_plan(samples, n_fft, hop, n_mels, n_dct=None):

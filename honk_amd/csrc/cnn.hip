@@ -912,6 +912,8 @@ __global__ __launch_bounds__(512, 1) void conv1f_kernel(Conv1FArgs a) {
   }
 }
 
+#include "cnn_split.inc"  // the latency schedule's kernels: the four convs above cut into small tiles, split-K Linear
+
 // conv1 in fp32 with conv2f following: trad-pool2's conv1 geometry
 static bool conv1f_applies(const honk_cnn_desc* d, int oh1, int ph1, int pw1) {
   if (const char* e = getenv("HONK_CNN_C1F"))
@@ -1454,17 +1456,24 @@ static int64_t chunk_clips(const Shapes& s, int64_t batch) {
 }
 
 // The forward's launch schedule: the per-call weight pack (L_PACK), then one step per
-// launch of a chunk.  honk_cnn_launch_plan reports it, honk_cnn_workspace_bytes sizes the
-// fragment region from it and honk_cnn_forward runs it: the _applies predicates are asked
-// here and nowhere else.
+// launch of a chunk.  honk_cnn_launch_plan / honk_cnn_latency_plan report it, the workspace
+// queries size the fragment and partial regions from it and the forwards run it: the
+// _applies predicates, the latency threshold and the split geometry are decided here and
+// nowhere else.
 enum Layer { L_PACK, L_CONV1, L_POOL1, L_CONV2, L_POOL2, L_LIN, L_DNN1, L_DNN2, L_OUT };
 struct Step {
-  int layer, kind;  // kind: HONK_CNN_KERNEL_*
+  int layer, kind;     // kind: HONK_CNN_KERNEL_*
+  int64_t tiles = 0;   // the launch's workgroups for `clips` clips (latency plans; 0 where it was not asked for)
+  int aux = 0;         // CONV1XS / CONV1FS: m-tiles per band; LINEAR_SPLITK / _SUM: K slices
+  int lds = 0;         // the split convs: LDS bytes of one half image / plane
 };
 struct Plan {
-  Step steps[12];
+  Step steps[16];
   int n = 0;
-  void add(int layer, int kind) { steps[n++] = Step{layer, kind}; }
+  Step& add(int layer, int kind) {
+    steps[n] = Step{layer, kind};
+    return steps[n++];
+  }
   bool has(int kind) const {
     for (int i = 0; i < n; ++i)
       if (steps[i].kind == kind) return true;
@@ -1477,41 +1486,178 @@ static int gemm_kind(bool x3, bool pool2, int nhwc_x3) {
          (nhwc_x3 == 1 ? HONK_CNN_GEMM_NHWC_BF16 : nhwc_x3 == 2 ? HONK_CNN_GEMM_NHWC_F32 : 0);
 }
 
-static Plan plan_forward(const honk_cnn_desc* d, const Shapes& s) {
+// ---- the latency schedule's decisions ----
+// Chunks of fewer clips than this run the split kernels: fewer clips than CUs (a dedicated
+// throughput kernel would leave CUs idle), and no more than the largest measured batch at which
+// the split schedule was not slower than the throughput one (cnn-trad-pool2
+// on an MI355X, 96 clips in fp32 and 64 in bf16x3 -- the one-wave conv2 tiles re-read their
+// weight fragments per tile, which the whole-clip kernels amortise over 13 m-tiles)
+constexpr int64_t LAT_MAX_BATCH_F32 = 96, LAT_MAX_BATCH_X3 = 64;
+static int64_t latency_threshold(int cus, bool x3) {
+  const int64_t cap = (x3 ? LAT_MAX_BATCH_X3 : LAT_MAX_BATCH_F32) + 1;
+  return cus < cap ? cus : cap;
+}
+
+// K slice of the split-K Linear: a function of (K, N) only, never of the batch or the device
+// (the sweep); a multiple of 4 so that 16-byte loads stay aligned
+constexpr int SK_SLICE = 1024;
+static int splitk_slice(int K, int N) {
+  (void)K; (void)N;
+  int sl = SK_SLICE;
+  if (const char* e = getenv("HONK_CNN_SPLITK_SLICE")) sl = atoi(e);  // (the sweep's knob)
+  if (sl < 4) sl = 4;
+  return (sl + 3) & ~3;
+}
+// K slices of a Linear on the split-K kernels, or 0: shorter than two slices
+static int splitk_slices(int K, int N) {
+  const int sl = splitk_slice(K, N);
+  return K >= 2 * sl ? (int)cdiv(K, sl) : 0;
+}
+
+// conv2, split: LDS bytes of one half image of the tallest tile (16 consecutive output pixels
+// span at most 15 / OW + 2 output rows), or 0 where two of them exceed C2S_LDS_MAX
+static int conv2s_half_bytes(const honk_cnn_desc* d, const Shapes& s) {
+  int rows = 15 / s.ow2 + 2 + d->c2_kh - 1;
+  if (rows > s.ph1) rows = s.ph1;
+  const int64_t hb = cdiv((int64_t)rows * s.pw1 * 8, 64) * 1024;
+  return 2 * hb <= C2S_LDS_MAX ? (int)hb : 0;
+}
+
+// conv1, split: rows of the tallest band of bm m-tiles
+static int conv1s_rows(const Shapes& s, int bm) {
+  const int nmt = s.ph1 * s.pw1 / 4;
+  int rows = 0;
+  for (int m0 = 0; m0 < nmt; m0 += bm) {
+    const int m1 = m0 + bm < nmt ? m0 + bm : nmt;
+    const int r = 2 * ((4 * m1 - 1) / s.pw1 - (4 * m0) / s.pw1) + 2 + C1X3_KH - 1;
+    if (r > rows) rows = r;
+  }
+  return rows;
+}
+constexpr int C1S_LDS_MAX = 64 * 1024;
+// m-tiles per band (a multiple of 4: one per wave): the largest that still gives every CU a
+// workgroup where the chunk yields that many (bands of 4 m-tiles x 2 n-groups), within the LDS
+static int conv1s_band_mtiles(const Shapes& s, int64_t clips, int cus, bool x3) {
+  const int nmt = s.ph1 * s.pw1 / 4;
+  const int64_t most = clips * cdiv(nmt, 4) * 2;
+  const int64_t want = most < cus ? most : cus;
+  int bm = 4;
+  while (bm + 4 <= ((nmt + 3) & ~3) && clips * cdiv(nmt, bm + 4) * 2 >= want) bm += 4;
+  const int per_row = x3 ? 2 * C1X3_COLS * 16 : C1F_COLS * 16;
+  while (bm > 4 && conv1s_rows(s, bm) * per_row > C1S_LDS_MAX) bm -= 4;
+  return bm;
+}
+
+// clips = 0: the throughput plan (tiles not filled).  clips > 0: the plan of a chunk of that
+// many clips on a device of `cus` CUs, with tiles; `latency` asks for the latency schedule,
+// which is the throughput plan at and above latency_threshold(cus, x3).
+static Plan plan_forward(const honk_cnn_desc* d, const Shapes& s, int64_t clips = 0, int cus = 0,
+                         bool latency = false) {
   Plan p;
   const bool x3 = d->precision == HONK_PREC_BF16X3;
+  const bool split = latency && clips > 0 && clips < latency_threshold(cus, x3);
   const bool c2x3 = conv2x3_applies(d, s.ph1, s.pw1, s.oh2, s.ow2);
   const bool c2f = conv2f_applies(d, s.ph1, s.pw1, s.oh2, s.ow2);
-  if (c2x3) p.add(L_PACK, HONK_CNN_KERNEL_PACK_CONV2X3);  // conv2 weights -> hi/lo fragments
-  if (c2f) p.add(L_PACK, HONK_CNN_KERNEL_PACK_CONV2F);    // conv2 weights -> fp32 fragments
+  const int64_t grid = clips < cus ? clips : cus;  // the dedicated throughput kernels' persistent grid
+  auto gemm_tiles = [&](int64_t M, int N) { return cdiv(M, BM) * cdiv(N, BN); };
+  if (c2x3)  // conv2 weights -> hi/lo fragments
+    p.add(L_PACK, HONK_CNN_KERNEL_PACK_CONV2X3).tiles = cdiv(2 * d->c2_kh * d->c2_kw * 4 * 2 * 64 * 8, 256);
+  if (c2f)   // conv2 weights -> fp32 fragments
+    p.add(L_PACK, HONK_CNN_KERNEL_PACK_CONV2F).tiles = cdiv(2 * d->c2_kh * d->c2_kw * 2 * 4 * 64 * 4, 256);
   // conv1 + ReLU (model.py:187), pool1 (:189; skipped when 1x1)
   const bool fuse1 = d->p1_h == 2 && d->p1_w == 2;  // conv1 + ReLU + MaxPool2d(2,2) in one kernel
-  if (c2f && conv1f_applies(d, s.oh1, s.ph1, s.pw1))
-    p.add(L_CONV1, HONK_CNN_KERNEL_CONV1F);
-  else if (c2x3 && conv1x3_applies(d, s.oh1, s.ph1, s.pw1))
-    p.add(L_CONV1, HONK_CNN_KERNEL_CONV1X3);
-  else
-    p.add(L_CONV1, gemm_kind(x3, fuse1, c2x3 ? 1 : c2f ? 2 : 0));
-  if (!fuse1 && d->p1_h * d->p1_w > 1) p.add(L_POOL1, HONK_CNN_KERNEL_MAXPOOL);
-  if (c2x3) {  // model.py:190-193 on the fast path (pool2 is 1x1)
-    p.add(L_CONV2, HONK_CNN_KERNEL_CONV2X3);
-  } else if (c2f) {
-    p.add(L_CONV2, HONK_CNN_KERNEL_CONV2F);
+  const bool c1f = c2f && conv1f_applies(d, s.oh1, s.ph1, s.pw1);
+  const bool c1x3 = !c1f && c2x3 && conv1x3_applies(d, s.oh1, s.ph1, s.pw1);
+  if ((c1f || c1x3) && split) {
+    Step& st = p.add(L_CONV1, c1f ? HONK_CNN_KERNEL_CONV1FS : HONK_CNN_KERNEL_CONV1XS);
+    st.aux = conv1s_band_mtiles(s, clips, cus, c1x3);
+    st.lds = conv1s_rows(s, st.aux) * (c1x3 ? C1X3_COLS : C1F_COLS) * 16;
+    st.tiles = clips * cdiv(s.ph1 * s.pw1 / 4, st.aux) * 2;
+  } else if (c1f || c1x3) {
+    p.add(L_CONV1, c1f ? HONK_CNN_KERNEL_CONV1F : HONK_CNN_KERNEL_CONV1X3).tiles = grid;
+  } else {
+    p.add(L_CONV1, gemm_kind(x3, fuse1, c2x3 ? 1 : c2f ? 2 : 0)).tiles =
+        gemm_tiles(fuse1 ? clips * s.ph1 * s.pw1 * 4 : clips * s.oh1 * s.ow1, d->c1_out);
+  }
+  if (!fuse1 && d->p1_h * d->p1_w > 1) p.add(L_POOL1, HONK_CNN_KERNEL_MAXPOOL).tiles = cdiv(clips * s.p1, 256);
+  if (c2x3 || c2f) {  // model.py:190-193 on the fast path (pool2 is 1x1)
+    const int hb = conv2s_half_bytes(d, s);
+    if (split && hb) {
+      Step& st = p.add(L_CONV2, c2x3 ? HONK_CNN_KERNEL_CONV2XS : HONK_CNN_KERNEL_CONV2FS);
+      st.lds = hb;
+      st.tiles = clips * cdiv(s.oh2 * s.ow2, 16) * cdiv(d->c2_out, 16);
+    } else {
+      p.add(L_CONV2, c2x3 ? HONK_CNN_KERNEL_CONV2X3 : HONK_CNN_KERNEL_CONV2F).tiles = grid;
+    }
   } else if (d->has_conv2) {
     const bool fuse2 = d->p2_h == 2 && d->p2_w == 2;
-    p.add(L_CONV2, gemm_kind(x3, fuse2, 0));
-    if (!fuse2 && d->p2_h * d->p2_w > 1) p.add(L_POOL2, HONK_CNN_KERNEL_MAXPOOL);
+    p.add(L_CONV2, gemm_kind(x3, fuse2, 0)).tiles =
+        gemm_tiles(fuse2 ? clips * s.ph2 * s.pw2 * 4 : clips * s.oh2 * s.ow2, d->c2_out);
+    if (!fuse2 && d->p2_h * d->p2_w > 1) p.add(L_POOL2, HONK_CNN_KERNEL_MAXPOOL).tiles = cdiv(clips * s.p2, 256);
   }
-  if (d->has_lin) p.add(L_LIN, linear_kind(32, x3));           // :195-196
-  if (d->dnn1) p.add(L_DNN1, linear_kind(d->dnn1, x3));        // :197-201
-  if (d->dnn2) p.add(L_DNN2, linear_kind(d->dnn2, x3));        // :202-204
-  p.add(L_OUT, linear_kind(d->n_labels, x3));                  // :205
+  int width = s.flat;
+  auto lin = [&](int layer, int n) {
+    const int S = split ? splitk_slices(width, n) : 0;
+    if (S) {  // a K of at least two slices: one partial per slice, then their sum
+      Step& a = p.add(layer, HONK_CNN_KERNEL_LINEAR_SPLITK);
+      a.aux = S;
+      a.tiles = (int64_t)S * cdiv(clips, SK_ROWS) * cdiv(n, SK_NB);
+      Step& b = p.add(layer, HONK_CNN_KERNEL_LINEAR_SPLITK_SUM);
+      b.aux = S;
+      b.tiles = cdiv(clips * n, 256);
+    } else {
+      const int kind = linear_kind(n, x3);
+      p.add(layer, kind).tiles = kind <= HONK_CNN_KERNEL_LINEAR_SMALL16 ? cdiv(clips, 4) : gemm_tiles(clips, n);
+    }
+    width = n;
+  };
+  if (d->has_lin) lin(L_LIN, 32);          // :195-196
+  if (d->dnn1) lin(L_DNN1, d->dnn1);       // :197-201
+  if (d->dnn2) lin(L_DNN2, d->dnn2);       // :202-204
+  lin(L_OUT, d->n_labels);                 // :205
   return p;
 }
 
 static size_t frag_bytes(const honk_cnn_desc* d, const Plan& p) {
   return (p.has(HONK_CNN_KERNEL_PACK_CONV2X3) ? conv2x3_frag_bytes(d) : 0) +
          (p.has(HONK_CNN_KERNEL_PACK_CONV2F) ? conv2f_frag_bytes(d) : 0);
+}
+
+// floats of the split-K partial region of a chunk of `clips` clips: the largest [S][clips][n]
+static int64_t partial_floats(const honk_cnn_desc* d, const Shapes& s, int64_t clips) {
+  int64_t m = 0;
+  int width = s.flat;
+  auto lin = [&](int n) {
+    const int64_t f = (int64_t)splitk_slices(width, n) * clips * n;
+    if (f > m) m = f;
+    width = n;
+  };
+  if (d->has_lin) lin(32);
+  if (d->dnn1) lin(d->dnn1);
+  if (d->dnn2) lin(d->dnn2);
+  lin(d->n_labels);
+  return m;
+}
+
+// y = act(x w^T + b) on the split-K kernels, two launches: the S slices' partials into `part`
+// ([S][m][n]), then their sum in ascending slice order + bias + ReLU
+static int splitk_partials(const float* x, const float* w, float* part, int64_t m, int k, int n, int S,
+                           hipStream_t st) {
+  if (m <= 0) return HONK_OK;
+  const int64_t rg = cdiv(m, SK_ROWS);
+  if (rg > 65535 || cdiv(n, SK_NB) > 65535)
+    return fail(HONK_ERR_ARG, "split-K Linear too large (m=%lld n=%d)", (long long)m, n);
+  hipLaunchKernelGGL(linear_splitk_kernel, dim3((unsigned)S, (unsigned)rg, (unsigned)cdiv(n, SK_NB)), dim3(256), 0, st,
+                     x, w, part, m, k, n, splitk_slice(k, n));
+  HONK_LAUNCH_CHECK("linear_splitk_kernel");
+  return HONK_OK;
+}
+static int splitk_sum(const float* part, const float* b, float* y, int64_t m, int n, int relu, int S, hipStream_t st) {
+  if (m <= 0) return HONK_OK;
+  hipLaunchKernelGGL(linear_splitk_sum_kernel, dim3((unsigned)cdiv(m * n, 256)), dim3(256), 0, st, part, b, y, m * n, n,
+                     S, relu);
+  HONK_LAUNCH_CHECK("linear_splitk_sum_kernel");
+  return HONK_OK;
 }
 
 }  // namespace cnn
@@ -1692,6 +1838,17 @@ size_t honk_cnn_workspace_bytes(const honk_cnn_desc* d, int64_t batch) {
   return (size_t)2 * chunk_clips(s, batch) * per_clip_floats(s) * sizeof(float) + frag_bytes(d, plan_forward(d, s));
 }
 
+// the latency schedule's workspace: the throughput one (activations, fragments) + the split-K partials
+static size_t latency_partial_bytes(const honk_cnn_desc* d, const Shapes& s, int64_t chunk) {
+  return (size_t)partial_floats(d, s, chunk < LAT_MAX_BATCH_F32 ? chunk : LAT_MAX_BATCH_F32) * sizeof(float);
+}
+
+size_t honk_cnn_latency_workspace_bytes(const honk_cnn_desc* d, int64_t batch) {
+  Shapes s;
+  if (shapes(d, &s) != HONK_OK || batch < 1) return 0;
+  return honk_cnn_workspace_bytes(d, batch) + latency_partial_bytes(d, s, chunk_clips(s, batch));
+}
+
 static int check_precision(const honk_cnn_desc* d) {
   if (d->precision != HONK_PREC_F32 && d->precision != HONK_PREC_BF16X3)
     return fail(HONK_ERR_UNSUPPORTED, "cnn path precision %d (f32 or bf16x3)", d->precision);
@@ -1709,23 +1866,75 @@ int honk_cnn_launch_plan(const honk_cnn_desc* d, int32_t* kinds, int32_t max_kin
   return p.n;
 }
 
-int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float* x, float* logits, int64_t batch,
-                     void* workspace, size_t ws_bytes, void* stream) {
+int64_t honk_cnn_latency_threshold(const honk_cnn_desc* d, int32_t n_cus) {
+  if (!d) return fail(HONK_ERR_ARG, "null descriptor");
+  const int rc = check_precision(d);
+  if (rc) return rc;
+  if (n_cus < 0) return fail(HONK_ERR_ARG, "negative CU count");
+  return latency_threshold(n_cus > 0 ? n_cus : cu_count(), d->precision == HONK_PREC_BF16X3);
+}
+
+int honk_cnn_latency_plan(const honk_cnn_desc* d, int64_t batch, int32_t n_cus, int32_t* kinds, int64_t* tiles,
+                          int32_t max_steps) {
+  Shapes s;
+  int rc = shapes(d, &s);
+  if (rc) return rc;
+  rc = check_precision(d);
+  if (rc) return rc;
+  if (batch < 1 || n_cus < 0) return fail(HONK_ERR_ARG, "latency plan of %lld clips on %d CUs", (long long)batch, n_cus);
+  const Plan p = plan_forward(d, s, chunk_clips(s, batch), n_cus > 0 ? n_cus : cu_count(), true);
+  for (int k = 0; k < p.n && k < max_steps; ++k) {
+    if (kinds) kinds[k] = p.steps[k].kind;
+    if (tiles) tiles[k] = p.steps[k].tiles;
+  }
+  return p.n;
+}
+
+int32_t honk_linear_splitk_slices(int32_t k, int32_t n) {
+  if (k < 1 || n < 1) return 0;
+  return splitk_slices(k, n);
+}
+
+size_t honk_linear_splitk_workspace_bytes(int64_t m, int32_t k, int32_t n) {
+  if (m < 1 || k < 1 || n < 1) return 0;
+  return (size_t)cdiv(k, splitk_slice(k, n)) * m * n * sizeof(float);
+}
+
+int honk_linear_splitk_f32(const float* x, const float* w, const float* b, float* y, int64_t m, int32_t k, int32_t n,
+                           int32_t relu, void* workspace, size_t ws_bytes, void* stream) {
+  if (k < 1 || n < 1 || m < 0) return fail(HONK_ERR_ARG, "bad linear shape");
+  if (m == 0) return HONK_OK;
+  if (!x || !w || !y) return fail(HONK_ERR_ARG, "null pointer argument");
+  const size_t need = honk_linear_splitk_workspace_bytes(m, k, n);
+  if (!workspace || ws_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
+  // (a K shorter than two slices, which the forward keeps on its throughput kernel, runs here as well)
+  const int S = (int)cdiv(k, splitk_slice(k, n));
+  int rc = splitk_partials(x, w, (float*)workspace, m, k, n, S, (hipStream_t)stream);
+  if (rc) return rc;
+  return splitk_sum((const float*)workspace, b, y, m, n, relu, S, (hipStream_t)stream);
+}
+
+// Both forwards and honk_cnn_features_f32: the checks, the per-call weight pack, then per chunk
+// the steps of its plan (latency: the plan of that chunk's clips on this device).  `features`
+// (logits NULL): stop before the first Linear and copy the flattened NCHW conv output out.
+static int run_forward(const honk_cnn_desc* d, const float* const* t, const float* x, float* logits, float* features,
+                       int64_t batch, void* workspace, size_t ws_bytes, void* stream, bool latency) {
   Shapes s;
   int rc = shapes(d, &s);
   if (rc) return rc;
   if (batch < 0) return fail(HONK_ERR_ARG, "negative batch");
   if (batch == 0) return HONK_OK;
-  if (!t || !x || !logits || !workspace) return fail(HONK_ERR_ARG, "null pointer argument");
+  if (!t || !x || !(logits || features) || !workspace) return fail(HONK_ERR_ARG, "null pointer argument");
   if (!t[0] || !t[1] || !t[10] || !t[11]) return fail(HONK_ERR_ARG, "conv1/output tensors are required");
   if (d->has_conv2 && (!t[2] || !t[3])) return fail(HONK_ERR_ARG, "conv2 tensors missing");
   if (d->has_lin && (!t[4] || !t[5])) return fail(HONK_ERR_ARG, "lin tensors missing");
   if (d->dnn1 && (!t[6] || !t[7])) return fail(HONK_ERR_ARG, "dnn1 tensors missing");
   if (d->dnn2 && (!t[8] || !t[9])) return fail(HONK_ERR_ARG, "dnn2 tensors missing");
   if (d->dnn2 && !d->dnn1) return fail(HONK_ERR_ARG, "dnn2 without dnn1");
-  const Plan plan = plan_forward(d, s);
+  const Plan base = plan_forward(d, s);  // (the pack steps and the fragment region are the same in both schedules)
   const int64_t chunk = chunk_clips(s, batch);
-  const size_t need = (size_t)2 * chunk * per_clip_floats(s) * sizeof(float) + frag_bytes(d, plan);
+  const size_t act = (size_t)2 * chunk * per_clip_floats(s) * sizeof(float) + frag_bytes(d, base);
+  const size_t need = act + (latency ? latency_partial_bytes(d, s, chunk) : 0);
   if (ws_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
   rc = check_precision(d);
   if (rc) return rc;
@@ -1734,14 +1943,15 @@ int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float*
   float* A = (float*)workspace;
   float* B = A + chunk * per_clip_floats(s);
   uint4* c2frag = (uint4*)(B + chunk * per_clip_floats(s));
+  float* part = (float*)((char*)workspace + act);
   const int ntap = d->c2_kh * d->c2_kw;
-  for (int i = 0; i < plan.n; ++i) {  // one small launch per call
-    if (plan.steps[i].kind == HONK_CNN_KERNEL_PACK_CONV2X3) {
+  for (int i = 0; i < base.n; ++i) {  // one small launch per call
+    if (base.steps[i].kind == HONK_CNN_KERNEL_PACK_CONV2X3) {
       const int total = 2 * ntap * 4 * 2 * 64 * 8;
       hipLaunchKernelGGL(pack_conv2x3_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, t[2],
                          (__bf16*)c2frag, d->c2_out, ntap);
       HONK_LAUNCH_CHECK("pack_conv2x3_kernel");
-    } else if (plan.steps[i].kind == HONK_CNN_KERNEL_PACK_CONV2F) {
+    } else if (base.steps[i].kind == HONK_CNN_KERNEL_PACK_CONV2F) {
       const int total = 2 * ntap * 2 * 4 * 64 * 4;
       hipLaunchKernelGGL(pack_conv2f_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, t[2], (float*)c2frag,
                          d->c2_out, ntap);
@@ -1752,6 +1962,7 @@ int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float*
   for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
     const int64_t n = (batch - c0 < chunk) ? batch - c0 : chunk;
     if (n > 0x7fffffff) return fail(HONK_ERR_ARG, "chunk too large");
+    const Plan plan = latency ? plan_forward(d, s, n, cu_count(), true) : base;
     const unsigned grid = (unsigned)(n < cu_count() ? n : cu_count());  // the dedicated kernels' persistent grid
     // ping-pong: every step reads cur and writes other (conv1: x -> A); flatten is free: NCHW (model.py:194)
     const float* cur = x + c0 * d->height * d->width;
@@ -1761,12 +1972,22 @@ int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float*
       cur = other;
       other = (cur == A) ? B : A;
     };
+    // a Linear step: its throughput kernel, or one of the split-K pair (the partials leave cur in place)
+    auto lin_step = [&](const Step& sp, const float* w, const float* b, float* y, int nout, int relu) {
+      if (sp.kind == HONK_CNN_KERNEL_LINEAR_SPLITK) return splitk_partials(cur, w, part, n, width, nout, sp.aux, st);
+      const int r = sp.kind == HONK_CNN_KERNEL_LINEAR_SPLITK_SUM ? splitk_sum(part, b, y, n, nout, relu, sp.aux, st)
+                                                                 : linear(cur, w, b, y, n, width, nout, relu, st, x3);
+      width = nout;
+      return r;
+    };
     for (int i = 0; i < plan.n; ++i) {
-      const int kind = plan.steps[i].kind;
+      const Step& sp = plan.steps[i];
+      const int kind = sp.kind;
       const bool gemm = (kind & HONK_CNN_KERNEL_GEMM) != 0;
       const bool pool = gemm && (kind & HONK_CNN_GEMM_POOL2);
+      if (features && sp.layer >= L_LIN) break;
       rc = HONK_OK;
-      switch (plan.steps[i].layer) {
+      switch (sp.layer) {
         case L_PACK:
           continue;
         case L_CONV1:
@@ -1786,6 +2007,19 @@ int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float*
             hipLaunchKernelGGL(conv1x3_kernel, dim3(grid), dim3(512), 0, st, c);
             tl.done(st);
             HONK_LAUNCH_CHECK("conv1x3_kernel");
+          } else if (kind == HONK_CNN_KERNEL_CONV1FS || kind == HONK_CNN_KERNEL_CONV1XS) {
+            const bool xs = kind == HONK_CNN_KERNEL_CONV1XS;
+            Conv1SArgs c;
+            c.x = cur; c.w = t[0]; c.bias = t[1]; c.out = other;
+            c.B = (int)n; c.H = d->height; c.W = d->width; c.PH = s.ph1; c.PW = s.pw1;
+            c.bm = sp.aux; c.nbands = (int)cdiv(s.ph1 * s.pw1 / 4, sp.aux); c.plane = sp.lds;
+            TimedLaunch tl(st, 2.0 * (double)n * s.ph1 * s.pw1 * 4 * 64 * C1X3_KH * C1X3_KW);
+            if (xs)
+              hipLaunchKernelGGL(conv1xs_kernel, dim3((unsigned)sp.tiles), dim3(256), 2 * sp.lds, st, c);
+            else
+              hipLaunchKernelGGL(conv1fs_kernel, dim3((unsigned)sp.tiles), dim3(256), sp.lds, st, c);
+            tl.done(st);
+            HONK_LAUNCH_CHECK("conv1 split kernel");
           } else {
             rc = conv(cur, t[0], t[1], other, n, 1, d->height, d->width, d->c1_out, d->c1_kh, d->c1_kw, d->c1_sh,
                       d->c1_sw, 1, st, pool, x3,
@@ -1814,6 +2048,19 @@ int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float*
             hipLaunchKernelGGL((conv2f_kernel<C2F_MT>), dim3(grid), dim3(256), 0, st, c);
             tl.done(st);
             HONK_LAUNCH_CHECK("conv2f_kernel");
+          } else if (kind == HONK_CNN_KERNEL_CONV2XS || kind == HONK_CNN_KERNEL_CONV2FS) {
+            Conv2SArgs c;
+            c.in = cur; c.wfrag = c2frag; c.bias = t[3]; c.out = other;
+            c.B = (int)n; c.PH = s.ph1; c.PW = s.pw1; c.KW = d->c2_kw; c.ntap = ntap;
+            c.OH = s.oh2; c.OW = s.ow2; c.N = d->c2_out;
+            c.nmt = (int)cdiv(s.oh2 * s.ow2, 16); c.nnt = (int)cdiv(d->c2_out, 16); c.half_bytes = sp.lds;
+            TimedLaunch tl(st, 2.0 * (double)n * s.oh2 * s.ow2 * d->c2_out * 64 * ntap);
+            if (kind == HONK_CNN_KERNEL_CONV2XS)
+              hipLaunchKernelGGL(conv2xs_kernel, dim3((unsigned)sp.tiles), dim3(64), 2 * sp.lds, st, c);
+            else
+              hipLaunchKernelGGL(conv2fs_kernel, dim3((unsigned)sp.tiles), dim3(64), 2 * sp.lds, st, c);
+            tl.done(st);
+            HONK_LAUNCH_CHECK("conv2 split kernel");
           } else {
             rc = conv(cur, t[2], t[3], other, n, d->c1_out, s.ph1, s.pw1, d->c2_out, d->c2_kh, d->c2_kw, d->c2_sh,
                       d->c2_sw, 1, st, pool, x3);
@@ -1823,26 +2070,41 @@ int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float*
           rc = maxpool(cur, other, n * d->c2_out, s.oh2, s.ow2, d->p2_h, d->p2_w, st);
           break;
         case L_LIN:
-          rc = linear(cur, t[4], t[5], other, n, width, 32, 0, st, x3);
-          width = 32;
+          rc = lin_step(sp, t[4], t[5], other, 32, 0);
           break;
         case L_DNN1:
-          rc = linear(cur, t[6], t[7], other, n, width, d->dnn1, d->dnn1_relu, st, x3);
-          width = d->dnn1;
+          rc = lin_step(sp, t[6], t[7], other, d->dnn1, d->dnn1_relu);
           break;
         case L_DNN2:
-          rc = linear(cur, t[8], t[9], other, n, width, d->dnn2, 0, st, x3);
-          width = d->dnn2;
+          rc = lin_step(sp, t[8], t[9], other, d->dnn2, 0);
           break;
         case L_OUT:
-          rc = linear(cur, t[10], t[11], logits + c0 * d->n_labels, n, width, d->n_labels, 0, st, x3);
+          rc = lin_step(sp, t[10], t[11], logits + c0 * d->n_labels, d->n_labels, 0);
           break;
       }
       if (rc) return rc;
-      wrote();
+      if (kind != HONK_CNN_KERNEL_LINEAR_SPLITK) wrote();
     }
+    if (features)
+      HONK_HIP_CHECK(hipMemcpyAsync(features + c0 * s.flat, cur, (size_t)n * s.flat * sizeof(float),
+                                    hipMemcpyDeviceToDevice, st));
   }
   return HONK_OK;
+}
+
+int honk_cnn_forward(const honk_cnn_desc* d, const float* const* t, const float* x, float* logits, int64_t batch,
+                     void* workspace, size_t ws_bytes, void* stream) {
+  return run_forward(d, t, x, logits, nullptr, batch, workspace, ws_bytes, stream, false);
+}
+
+int honk_cnn_forward_latency(const honk_cnn_desc* d, const float* const* t, const float* x, float* logits,
+                             int64_t batch, void* workspace, size_t ws_bytes, void* stream) {
+  return run_forward(d, t, x, logits, nullptr, batch, workspace, ws_bytes, stream, true);
+}
+
+int honk_cnn_features_f32(const honk_cnn_desc* d, const float* const* t, const float* x, float* features,
+                          int64_t batch, void* workspace, size_t ws_bytes, void* stream, int32_t latency) {
+  return run_forward(d, t, x, nullptr, features, batch, workspace, ws_bytes, stream, latency != 0);
 }
 
 }  // extern "C"

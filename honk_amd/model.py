@@ -150,12 +150,12 @@ def _state_key(tensors, device):
 
 
 class CapturedForward:
-    """A captured stream-ordered forward (``SpeechResModel.honk_capture``).
+    """A captured stream-ordered forward (``SpeechResModel.honk_capture``, ``SpeechModel.honk_capture``).
 
     ``replay(x)`` (also ``__call__``) copies ``x`` into the graph's input buffer, replays
     the graph on the current stream and returns ``logits``: the graph's STATIC output
     tensor, which the next replay overwrites (clone it to keep a result).  ``flagged`` is
-    the static 0-dim int32 device tensor holding the last replay's flagged-clip count.
+    the static 0-dim int32 device tensor holding the last replay's flagged-clip count (cnn: None).
     Nothing here synchronises."""
 
     def __init__(self, graph, x, logits, flagged, packed):
@@ -610,6 +610,11 @@ class SpeechModel(SerializableModule):
         self.honk_reroute = True
         # training on ROCm tensors: convs + ReLU and max-pools on the gfx950 kernels (False: MIOpen)
         self.honk_native_train = True
+        # "throughput": honk_cnn_forward (a workgroup owns whole clips).  "latency":
+        # honk_cnn_forward_latency -- batches of fewer clips than the device has CUs run the
+        # dedicated convs split over all CUs (the conv stack bit for bit) and the long Linears
+        # split over K (the same 1e-4 bar); larger batches run the throughput schedule.
+        self.honk_schedule = "throughput"
 
     # -- reference forward (CPU tensors / training mode): model.py:186-205 --
     # native: training on a ROCm tensor runs relu(conv) and the max-pools on the
@@ -687,6 +692,9 @@ class SpeechModel(SerializableModule):
             prec = "bf16x3"
         if prec not in ("f32", "bf16x3"):
             raise ValueError("SpeechModel.honk_precision must be 'auto', 'f32' or 'bf16x3'")
+        if self.honk_schedule not in ("throughput", "latency"):
+            raise ValueError("honk_schedule must be 'throughput' or 'latency'")
+        latency = self.honk_schedule == "latency"
         self.honk_last_precision = prec
         desc = _native.CnnDesc(**d, precision=_native.PRECISIONS[prec])
         B = x.shape[0]
@@ -694,14 +702,44 @@ class SpeechModel(SerializableModule):
             out = torch.empty(B, d["n_labels"], dtype=torch.float32, device=x.device)
             if B == 0:
                 return out
-            ws_bytes = lib.honk_cnn_workspace_bytes(desc, B)
+            ws_query = "honk_cnn_latency_workspace_bytes" if latency else "honk_cnn_workspace_bytes"
+            entry = "honk_cnn_forward_latency" if latency else "honk_cnn_forward"
+            ws_bytes = getattr(lib, ws_query)(desc, B)
             if ws_bytes == 0:
-                _native.check(-1, "honk_cnn_workspace_bytes")
+                _native.check(-1, ws_query)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-            _native.check(lib.honk_cnn_forward(desc, _native.ptr_array(ts), x.data_ptr(), out.data_ptr(), B,
-                                               ws.data_ptr(), ws_bytes, _native.stream_handle(x.device)),
-                          "honk_cnn_forward")
+            _native.check(getattr(lib, entry)(desc, _native.ptr_array(ts), x.data_ptr(), out.data_ptr(), B,
+                                              ws.data_ptr(), ws_bytes, _native.stream_handle(x.device)),
+                          entry)
         return out
+
+    def honk_capture(self, x_example):
+        """Capture the eval forward for inputs shaped like ``x_example`` (a non-empty float32 ROCm
+        tensor [B, H, W]; eval mode) in a ``torch.cuda.CUDAGraph`` and return a
+        ``CapturedForward``: ``replay(x) -> logits`` (its ``flagged`` is None: the cnn forward has
+        no admission count).
+
+        One eager forward runs first -- the CU-count query of the schedule happens there, outside
+        the capture -- then the capture records the launches of ``honk_cnn_forward``
+        (``honk_schedule = "latency"``: ``honk_cnn_forward_latency``) on the capture stream.  The
+        graph reads the parameter tensors in place and re-packs conv2's fragments inside every
+        replay, so an in-place weight update (``load()``, an optimiser step) is seen by the next
+        replay.  A NEW parameter tensor (a module moved or cast, a parameter replaced), another
+        ``honk_precision`` or another ``honk_schedule`` needs a new capture."""
+        if self.training:
+            raise RuntimeError("honk_capture needs eval mode (module.eval())")
+        if not (torch.is_tensor(x_example) and x_example.is_cuda and x_example.dim() == 3
+                and x_example.dtype == torch.float32 and x_example.shape[0] > 0):
+            raise RuntimeError("honk_capture expects a non-empty float32 [B, H, W] tensor on a ROCm device")
+        with torch.no_grad(), torch.cuda.device(x_example.device):
+            static_x = x_example.detach().clone().contiguous()
+            self(static_x)
+            torch.cuda.synchronize(static_x.device)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                static_out = self(static_x)
+            keep = [t for t in self._native_tensors() if t is not None]  # the weights the graph reads
+        return CapturedForward(graph, static_x, static_out, None, keep)
 
     def forward(self, x):
         if _native_ready(x, self):

@@ -48,18 +48,23 @@ class LabelService(object):
         raise NotImplementedError
 
 
+# the models with honk_schedule and honk_capture
+_SCHEDULED = (model.SpeechResModel, model.SpeechModel)
+
+
 class TorchLabelService(LabelService):
     """service.py:72-104 (hard-wired cnn-trad-pool2, like the reference).
 
-    ``honk_graph`` (opt-in, default False): with a ``SpeechResModel`` as ``self.model`` on a
-    ROCm device, ``label()`` replays a captured batch-1 stream-ordered forward
-    (``SpeechResModel.honk_capture``, captured at the first call) instead of launching the
-    forward's kernels one by one; ``reload()`` drops the capture.
+    ``honk_graph`` (opt-in, default False): with the model on a ROCm device (the ``SpeechModel``
+    ``reload()`` builds, or a ``SpeechResModel`` put in its place), ``label()`` replays a captured
+    batch-1 forward (the model's ``honk_capture``, captured at the first call) instead of
+    launching the forward's kernels one by one; ``reload()`` drops the capture.
 
-    ``honk_latency`` (opt-in, default False): with a ``SpeechResModel`` as ``self.model``, ``label()``,
-    ``label_batch()``, ``label_stream()`` (and a ``StreamListener`` on this service) run the model's
-    latency schedule (``SpeechResModel.honk_schedule = "latency"``: a small batch split over all
-    CUs, the same logits); with ``honk_graph``, ``label()`` replays a capture of that schedule.
+    ``honk_latency`` (opt-in, default False): ``label()``, ``label_batch()``, ``label_stream()`` (and a
+    ``StreamListener`` on this service) run the model's latency schedule (``honk_schedule =
+    "latency"``: a small batch split over all CUs -- a ``SpeechResModel``'s logits bit for bit, a
+    ``SpeechModel``'s within the 1e-4 bar); with ``honk_graph``, ``label()`` replays a capture of
+    that schedule.
 
     ``audio_preprocess_type`` ("MFCCs", the default, or "PCEN"): the front end the checkpoint was
     trained with (the reference's ``--audio_preprocess_type``).  PCEN restarts its smoother for every
@@ -82,7 +87,7 @@ class TorchLabelService(LabelService):
         self.reload()
 
     def reload(self):
-        self._honk_captured = None
+        self._honk_captured = self._honk_cnn_captured = None
         config = model.find_config(model.ConfigType.CNN_TRAD_POOL2)
         config["n_labels"] = len(self.labels)  # mutates the shared dict, as service.py:82 does
         self.model = model.SpeechModel(config)
@@ -107,19 +112,22 @@ class TorchLabelService(LabelService):
     def _net(self):
         """self.model, on the latency schedule where honk_latency asks for it."""
         m = self.model
-        if self.honk_latency and isinstance(m, model.SpeechResModel) and m.honk_schedule != "latency":
+        if self.honk_latency and isinstance(m, _SCHEDULED) and m.honk_schedule != "latency":
             m.honk_schedule = "latency"
-            self._honk_captured = None  # (a capture holds the schedule it was made with)
+            self._honk_captured = self._honk_cnn_captured = None  # (a capture holds the schedule it was made with)
         return m
 
     def _forward1(self, model_in):
         """The model's forward of label()'s batch-1 input: the captured one where honk_graph asks for it."""
         m = self._net()
-        if not (self.honk_graph and isinstance(m, model.SpeechResModel) and model_in.is_cuda and not m.training):
+        if not (self.honk_graph and isinstance(m, _SCHEDULED) and model_in.is_cuda and not m.training):
             return m(model_in)
-        cap = getattr(self, "_honk_captured", None)
+        # (model, CapturedForward): a res model's in _honk_captured, a SpeechModel's in _honk_cnn_captured
+        slot = "_honk_captured" if isinstance(m, model.SpeechResModel) else "_honk_cnn_captured"
+        cap = getattr(self, slot, None)
         if cap is None or cap[0] is not m or tuple(cap[1].x.shape) != tuple(model_in.shape):
-            cap = self._honk_captured = (m, m.honk_capture(model_in))
+            cap = (m, m.honk_capture(model_in))
+            setattr(self, slot, cap)
         return cap[1].replay(model_in)
 
     def label(self, wav_data):

@@ -308,6 +308,63 @@ int honk_cnn_launch_plan(const honk_cnn_desc* d, int32_t* kinds, int32_t max_kin
 int honk_cnn_forward(const honk_cnn_desc* d, const float* const* tensors, const float* x,
                      float* logits, int64_t batch, void* workspace, size_t workspace_bytes,
                      void* stream);
+/*
+ * The LATENCY schedule of the same forward, for batches smaller than the device's CU count.
+ * honk_cnn_forward is planned for throughput: the four hand-scheduled kernels give a workgroup
+ * a whole clip, a few-output Linear is one workgroup per 4 clips with the whole K serial in it,
+ * and a wider Linear is one GEMM block per 128 clips.  Here a chunk of fewer clips than
+ * honk_cnn_latency_threshold runs
+ *   - each dedicated conv of the throughput plan as its split form: conv2 in tiles of (clip,
+ *     16-pixel m-tile, 16-channel out tile), one wave each, staging only the image rows the tile
+ *     reaches; conv1 in tiles of (clip, band of pooled m-tiles, 2 out tiles), at least one per
+ *     CU where the chunk yields that many (bands of 4 m-tiles).  Per output element the MFMAs,
+ *     their order, the fragments and the epilogue are the throughput kernel's: the conv stack's
+ *     output is BIT FOR BIT the same (honk_cnn_features_f32 lets a test compare it);
+ *   - each Linear whose K spans at least two slices as split-K: workgroup (slice, 4 rows, 8
+ *     outputs) writes an fp32 partial [slice][row][n] into the workspace, a second launch adds
+ *     the partials in ascending slice order, then the bias, then the ReLU.  No atomics; the slice
+ *     length depends on (K, n) only, so a clip's logits depend neither on the batch around it
+ *     nor on the device.  fp32 fmaf accumulation in both precisions: NOT bit-equal to
+ *     honk_cnn_forward (the sums are associated differently), within the same 1e-4 bar;
+ *   - everything else (the generic GEMM convs, maxpool_kernel, the weight pack, a shorter
+ *     Linear) on its throughput kernel.
+ * A dedicated kernel switched off (HONK_CNN_C1F / C1X3 / C2F / C2X3 = 0) has no split form
+ * either; a conv2 tile whose two half images exceed 64 KiB of LDS stays on the throughput kernel.
+ * Chunks of at least honk_cnn_latency_threshold clips run the throughput plan unchanged: there
+ * the logits are bit for bit honk_cnn_forward's.
+ *
+ * honk_cnn_forward_latency: honk_cnn_forward's contract in every respect (the 12 tensors,
+ * enqueue only -- no synchronisation, capturable --, status codes and refusals, batch == 0
+ * writes nothing) with the workspace of honk_cnn_latency_workspace_bytes (activations,
+ * fragments, split-K partials; a workspace one byte short is refused with nothing enqueued).
+ * honk_cnn_latency_plan: the launches of one chunk of `batch` clips on a device of n_cus CUs
+ * (0: ask the device) -- kinds[i] = HONK_CNN_KERNEL_*, tiles[i] = the launch's workgroups;
+ * either may be NULL; up to max_steps written.  Returns the launch count or a (negative)
+ * HONK_ERR_* code, refusing what honk_cnn_launch_plan refuses.  The forward runs the very
+ * list this reports.  honk_cnn_latency_threshold: min(n_cus, 1 + the largest measured batch at
+ * which the split schedule was not slower: 96 clips in F32, 64 in BF16X3; only d->precision is
+ * read).  The three queries are host-only (n_cus > 0).
+ */
+#define HONK_CNN_KERNEL_CONV1XS 13       /* conv1xs_kernel: conv1x3_kernel, split               */
+#define HONK_CNN_KERNEL_CONV1FS 14       /* conv1fs_kernel: conv1f_kernel, split                */
+#define HONK_CNN_KERNEL_CONV2XS 15       /* conv2xs_kernel: conv2x3_kernel, split               */
+#define HONK_CNN_KERNEL_CONV2FS 32       /* conv2fs_kernel: conv2f_kernel, split                */
+#define HONK_CNN_KERNEL_LINEAR_SPLITK 33 /* linear_splitk_kernel (the K slices' partials)       */
+#define HONK_CNN_KERNEL_LINEAR_SPLITK_SUM 34 /* linear_splitk_sum_kernel (+ bias, ReLU)         */
+int honk_cnn_forward_latency(const honk_cnn_desc* d, const float* const* tensors, const float* x,
+                             float* logits, int64_t batch, void* workspace, size_t workspace_bytes,
+                             void* stream);
+size_t honk_cnn_latency_workspace_bytes(const honk_cnn_desc* d, int64_t batch);
+int honk_cnn_latency_plan(const honk_cnn_desc* d, int64_t batch, int32_t n_cus, int32_t* kinds,
+                          int64_t* tiles, int32_t max_steps);
+int64_t honk_cnn_latency_threshold(const honk_cnn_desc* d, int32_t n_cus);
+/* Exported for tests: the conv / pool steps of either schedule (latency = 0: honk_cnn_forward's,
+   1: honk_cnn_forward_latency's), stopping before the first Linear: features[batch][flat] fp32
+   in the flatten order of model.py:194 (NCHW).  Workspace: honk_cnn_latency_workspace_bytes
+   (latency = 0 takes honk_cnn_workspace_bytes as well). */
+int honk_cnn_features_f32(const honk_cnn_desc* d, const float* const* tensors, const float* x,
+                          float* features, int64_t batch, void* workspace, size_t workspace_bytes,
+                          void* stream, int32_t latency);
 
 /* ---- layer-level operators (used by the cnn driver; exported for tests) ------- */
 /* out[b][n][oh][ow] = act(bias[n] + sum_{ci,kh,kw} in[b][ci][oh*sh+kh][ow*sw+kw] * w[n][ci][kh][kw]) */
@@ -320,6 +377,17 @@ int honk_maxpool2d_f32(const float* in, float* out, int64_t batch, int32_t c, in
 /* y[m][n] = act(b[n] + sum_k x[m][k] * w[n][k])  (nn.Linear) */
 int honk_linear_f32(const float* x, const float* w, const float* b, float* y, int64_t m, int32_t k,
                     int32_t n, int32_t relu, void* stream);
+/* The same Linear on the latency schedule's split-K kernels (few rows m): fp32 partials
+   [slice][m][n] in the workspace, summed in ascending slice order, then bias, then ReLU.
+   honk_linear_splitk_slices: the K slices of a (k, n) Linear -- a function of k and n only -- or
+   0 where k is shorter than two slices (the forward keeps such a layer on its throughput kernel;
+   this call runs it all the same, in ceil(k / slice) slices).  Workspace:
+   honk_linear_splitk_workspace_bytes. */
+int32_t honk_linear_splitk_slices(int32_t k, int32_t n);
+size_t honk_linear_splitk_workspace_bytes(int64_t m, int32_t k, int32_t n);
+int honk_linear_splitk_f32(const float* x, const float* w, const float* b, float* y, int64_t m,
+                           int32_t k, int32_t n, int32_t relu, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* ---- SpeechModel training (utils/train.py:123-135 on the cnn configs) ----------- */
 /*
