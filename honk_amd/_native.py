@@ -189,6 +189,12 @@ _PROTOS = {
                                              ctypes.c_size_t, ctypes.c_void_p]),
     "honk_pcen_f32": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                      c_f32p, ctypes.c_int32, ctypes.c_void_p, c_f32p, ctypes.c_void_p]),
+    "honk_pcen_windows_plan": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int32] * 5 + [ctypes.c_int64] * 2
+                               + [ctypes.c_void_p]),
+    "honk_pcen_windows_i16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                             c_f32p, ctypes.c_int32, ctypes.c_void_p, c_f32p, ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.c_void_p]),
     "honk_spatial_mean_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_spatial_mean_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_cross_entropy_f32": (ctypes.c_int, [c_f32p, ctypes.c_void_p, c_f32p, ctypes.c_int64, ctypes.c_int32,

@@ -19,7 +19,8 @@ model.py:253-265): PARITY UNPINNED as well -- the reference's ``pcen`` package
 for every clip; ``out = (E / (M + eps)^alpha + delta)^r - delta^r``, [frames, n_mels], no DCT.
 The defaults (``PCEN_DEFAULTS``) follow that package as best they can be restated without it;
 pinning its exact choices later changes defaults, not code.  CPU path: numpy
-(``compute_pcen``); ROCm path: ``compute_pcen_batch`` -> ``honk_pcen_f32`` (csrc/pcen.hip).
+(``compute_pcen``); ROCm path: ``compute_pcen_batch`` -> ``honk_pcen_f32`` (csrc/pcen.hip), and for the
+strided windows of one recording ``compute_pcen_windows`` -> ``honk_pcen_windows_i16``.
 Checked against the independent float64 restatement tests/pcen_ref.py.
 """
 from __future__ import annotations
@@ -259,6 +260,73 @@ class AudioPreprocessor(object):
             x = (pcm.float() * (1.0 / 32768.0)).unfold(0, window, stride)[first:first + count]
             return self.compute_mfccs_batch(x.contiguous())
         _native.check(rc, "honk_mfcc_windows_i16")
+        return out
+
+    # -- PCEN of the same windows (libhonk_hip.so honk_pcen_windows_i16) ------------------
+    def pcen_windows_plan(self, samples, stride, window=16000, first=0, count=0):
+        """honk_pcen_windows_plan for this front end's n_fft / hop / n_mels -> (status, MfccWindowsPlan);
+        host-only."""
+        from . import _native
+        plan = _native.MfccWindowsPlan()
+        rc = _native.load().honk_pcen_windows_plan(int(samples), int(window), int(stride), self.n_fft,
+                                                   self.hop_length, self._mel.shape[0], int(first), int(count),
+                                                   ctypes.addressof(plan))
+        return rc, plan
+
+    def compute_pcen_windows(self, pcm, stride, window=16000, first=0, count=None):
+        """pcm: 1-D int16 torch tensor, one recording -> [count, frames, n_mels] float32: the PCEN
+        (``self.pcen_params``) of the windows ``pcm[w*stride : w*stride + window] / 32768`` for w in
+        [first, first + count) (count None: up to the recording's last whole window), each with its own
+        reflect padding and its own smoother.
+
+        ROCm device: honk_pcen_windows_i16 (csrc/mfcc_stream.hip; the mel energies of each STFT frame
+        once where stride % hop == 0, then a scan per window), nothing sliced on the host; a shape the
+        call refuses as unsupported goes through ``compute_pcen_batch`` on the unfolded windows.
+        CPU: ``compute_pcen`` per window."""
+        import torch
+        from . import _native
+        if pcm.dim() != 1 or pcm.dtype != torch.int16:
+            raise ValueError("compute_pcen_windows: pcm must be a 1-D int16 tensor")
+        stride, window, first = int(stride), int(window), int(first)
+        if stride < 1 or window < 1 or first < 0:
+            raise ValueError("compute_pcen_windows: stride >= 1, window >= 1, first >= 0")
+        S = pcm.shape[0]
+        W = 0 if S < window else 1 + (S - window) // stride
+        count = max(0, W - first) if count is None else int(count)
+        if count < 0 or first + count > W:
+            raise ValueError(f"compute_pcen_windows: windows [{first}, {first + count}) of {W}")
+        frames, n_mels = self.n_frames(window), self._mel.shape[0]
+        if not pcm.is_cuda:
+            x = pcm.numpy()
+            if count == 0:
+                return torch.empty(0, frames, n_mels, dtype=torch.float32)
+            return torch.cat([self.compute_pcen(x[w * stride:w * stride + window].astype(np.float32) / 32768.)
+                              for w in range(first, first + count)])
+        pcm = pcm.contiguous()
+        if count == 0:
+            return torch.empty(0, frames, n_mels, dtype=torch.float32, device=pcm.device)
+
+        def per_window():  # HONK_ERR_UNSUPPORTED: a shape outside the kernels' plan -> the per-window kernel
+            x = (pcm.float() * (1.0 / 32768.0)).unfold(0, window, stride)[first:first + count]
+            return self.compute_pcen_batch(x.contiguous())
+
+        rc, plan = self.pcen_windows_plan(S, stride, window, first, count)
+        if rc == -2:
+            return per_window()
+        _native.check(rc, "honk_pcen_windows_plan")
+        win, mel, _ = self._device_tables(pcm.device)
+        ws = self._windows_workspace(pcm.device, plan.workspace_bytes)
+        out = torch.empty(count, frames, n_mels, dtype=torch.float32, device=pcm.device)
+        p = self.pcen_params
+        params = _native.PcenParams(p["eps"], p["s"], p["alpha"], p["delta"], p["r"], int(p["power"]))
+        with torch.cuda.device(pcm.device):
+            rc = _native.load().honk_pcen_windows_i16(
+                pcm.data_ptr(), S, window, stride, first, count, win.data_ptr(), self.n_fft, self.hop_length,
+                mel.data_ptr(), n_mels, ctypes.addressof(params), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                _native.stream_handle(pcm.device))
+        if rc == -2:
+            return per_window()
+        _native.check(rc, "honk_pcen_windows_i16")
         return out
 
     def _windows_workspace(self, device, nbytes):

@@ -21,7 +21,20 @@
 // depends on its own n_fft samples only, in a fixed order.  Power goes to an LDS tile;
 // mel, log and DCT are fixed-order loops over that tile (no floating-point atomics);
 // the finished frames are scattered from LDS to every (window, frame) that maps to them.
+//
+// PCEN over the same windows (honk_pcen_windows_i16): the kernel above with another
+// epilogue, then a scan per window.  The mel energies E[f][m] of a frame are a function of
+// its n_fft samples alone, so stage 1 stores each frame's E row ONCE (no fan-out): on the
+// overlapping shared route into the workspace -- [G][n_mels] shared rows indexed by the
+// virtual window's frame, then [n][head + tail][n_mels] edge rows -- and on the gapped and
+// unshared routes, where every frame belongs to one window, straight into that window's
+// rows of out.  Stage 2 (pcen_windows_scan_kernel, one workgroup per window) gathers the
+// window's [frames][n_mels] tile into LDS, runs pcen_scan.h's segmented scan on it (M[0] =
+// E[0] of the window's own reflected frame 0: the smoother restarts per window) and writes
+// the window's rows of out once; the whole tile is read before any of it is written, so the
+// in-place routes are safe.
 #include "common.h"
+#include "pcen_scan.h"
 
 namespace honk {
 namespace mfccs {
@@ -36,6 +49,9 @@ constexpr int PADK = 8;      // floats inserted after every hop samples of a sta
 constexpr int MAX_MELS = 128;  // the mel-range table of the (fixed-size) workspace
 
 enum { MODE_UNSHARED = 0, MODE_OVERLAP = 1, MODE_GAPPED = 2 };
+// the epilogue of the frame-tile kernel: MFCC frames fanned out to their windows, or the mel
+// energies of |X| (power 1) / |X|^2 (power 2), each frame's row stored once
+enum { EPI_MFCC = 0, EPI_PCEN1 = 1, EPI_PCEN2 = 2 };
 
 struct Args {
   const int16_t* pcm;
@@ -43,7 +59,7 @@ struct Args {
   const float* melw;    // [n_mels][n_bins]
   const float* dct;     // [n_dct][n_mels]
   const int* mrange;    // [n_mels][2] first, last nonzero bin of a mel row (workspace)
-  float* out;           // [n][frames][n_dct]
+  float* out;           // [n][frames][n_dct]; PCEN epilogues: where the E rows go (header comment)
   int64_t first_sample;  // first_window * stride
   int64_t n;             // windows of the range
   int64_t G;             // MODE_OVERLAP: shared frames of the range
@@ -121,6 +137,7 @@ __global__ __launch_bounds__(64) void mel_range_kernel(const float* melw, int n_
   }
 }
 
+template <int EPI>
 __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int N = a.n_fft, NB = a.n_bins, NM = a.n_mels, ND = a.n_dct, hop = a.hop, pad = N / 2;
@@ -205,12 +222,49 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
 #pragma unroll
       for (int qq = 0; qq < 2; ++qq) {
         const int bb = 8 * ct + 2 * g + qq;
-        if (bb < NB)
-          pw[(16 * m + i16) * PS + bb] = acc[m][2 * qq] * acc[m][2 * qq] + acc[m][2 * qq + 1] * acc[m][2 * qq + 1];
+        if (bb < NB) {
+          float pv = acc[m][2 * qq] * acc[m][2 * qq] + acc[m][2 * qq + 1] * acc[m][2 * qq + 1];
+          if constexpr (EPI == EPI_PCEN1) pv = sqrtf(pv);
+          pw[(16 * m + i16) * PS + bb] = pv;
+        }
       }
     }
   }
   __syncthreads();
+  if constexpr (EPI != EPI_MFCC) {
+    // E = mel x |X|^power over each row's nonzero bins, ascending; a frame's row leaves once, coalesced
+    for (int e = tid; e < FT * NM; e += blockDim.x) {
+      const int f = e % FT, m = e / FT;
+      const float* w = a.melw + (int64_t)m * NB;
+      const int lo = a.mrange[2 * m], hi = a.mrange[2 * m + 1];
+      float s = 0.f;
+      for (int k = lo; k <= hi; ++k) s = fmaf(w[k], pw[f * PS + k], s);
+      lm[f * (NM + 1) + m] = s;
+    }
+    int64_t* erow = (int64_t*)(lm + FT * (NM + 1));  // [FT] the slot's row of a.out, -1: none (8-byte aligned)
+    if (tid < FT) {
+      const int gi = tid / gs, fi = tid - gi * gs;
+      int64_t row = -1;
+      if (gi < ng) {
+        const Group gr = group_of(a, t, gi);
+        if (fi < gr.nf) {
+          if (a.mode != MODE_OVERLAP)
+            row = gr.wl * a.frames + gr.f0 + fi;
+          else if (!edge)
+            row = gr.f0 - a.flo + fi;
+          else
+            row = a.G + gr.wl * (a.flo + a.frames - 1 - a.fhi) + (gr.f0 > a.fhi ? a.flo : 0) + fi;
+        }
+      }
+      erow[tid] = row;
+    }
+    __syncthreads();
+    for (int e = tid; e < FT * NM; e += blockDim.x) {
+      const int s = e / NM, m = e - s * NM;
+      if (erow[s] >= 0) a.out[erow[s] * NM + m] = lm[s * (NM + 1) + m];
+    }
+    return;
+  }
   // mel filterbank over each row's nonzero bins, ascending; log of the positive entries
   for (int e = tid; e < FT * NM; e += blockDim.x) {
     const int f = e % FT, m = e / FT;
@@ -265,6 +319,39 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
   }
 }
 
+// ---- PCEN stage 2 -------------------------------------------------------------------- //
+constexpr int SCAN_THREADS = 256;  // scan segments per band: SCAN_THREADS / n_mels (of the shape only)
+
+struct ScanArgs {
+  const float* e;  // MODE_OVERLAP: the workspace's E rows; else unused (E is in out)
+  float* out;      // [n][frames][n_mels]
+  int64_t G;
+  int frames, n_mels, flo, fhi, q, mode, nseg;
+};
+
+// one workgroup per window: E tile -> LDS, smoother + compression there, the window's rows out
+__global__ __launch_bounds__(SCAN_THREADS) void pcen_windows_scan_kernel(ScanArgs s, pcen::Params p) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];  // [frames][n_mels], then summ [nseg][n_mels]
+  const int F = s.frames, NM = s.n_mels;
+  const int64_t w = blockIdx.x;
+  float* o = s.out + w * F * NM;
+  if (s.mode == MODE_OVERLAP) {
+    const int ne = s.flo + F - 1 - s.fhi;
+    const int64_t erow = s.G + w * ne, srow = w * s.q - s.flo;
+    for (int i = threadIdx.x; i < F * NM; i += blockDim.x) {
+      const int f = i / NM, m = i - f * NM;
+      const int64_t row = f < s.flo ? erow + f : (f > s.fhi ? erow + s.flo + (f - s.fhi - 1) : srow + f);
+      tile[i] = s.e[row * NM + m];
+    }
+  } else {
+    for (int i = threadIdx.x; i < F * NM; i += blockDim.x) tile[i] = o[i];
+  }
+  __syncthreads();
+  pcen::scan_bands(tile, F, NM, 0, NM, s.nseg, tile + F * NM, p);
+  __syncthreads();
+  for (int i = threadIdx.x; i < F * NM; i += blockDim.x) o[i] = tile[i];
+}
+
 struct Plan {
   honk_mfcc_windows_plan_t p;
   int flo, fhi, mode, q, gs;
@@ -307,6 +394,67 @@ static int make_plan(int64_t samples, int32_t window, int32_t stride, int32_t n_
   return HONK_OK;
 }
 
+// host-only: the tiles and the LDS plan of the frame-tile kernel for a range (the shape fields of *a;
+// the caller sets the pointers, n_mels and n_dct).  tail_floats: what the epilogue keeps in the span area
+static int layout(const Plan& pl, const char* who, int32_t window, int32_t stride, int64_t first_window,
+                  int64_t n_windows, int32_t n_fft, int32_t hop, int tail_floats, Args* ap, int64_t* tiles,
+                  size_t* lds) {
+  Args& a = *ap;
+  a.first_sample = first_window * stride;
+  a.n = n_windows;
+  a.stride = stride; a.win_len = window; a.n_fft = n_fft; a.hop = hop; a.n_bins = n_fft / 2 + 1;
+  a.frames = pl.p.frames;
+  a.flo = pl.flo; a.fhi = pl.fhi; a.mode = pl.mode; a.q = pl.q;
+  a.G = pl.p.shared_frames;
+  a.tps = 1; a.gs = 1; a.gpt = 0; a.gspan = 0;
+  int64_t edge_tiles = 0;
+  const int seg_floats = (FT - 1) * hop + n_fft + PADK * (FT + n_fft / hop);
+  int xs = seg_floats;
+  if (pl.mode == MODE_OVERLAP) {
+    a.seg_tiles = cdiv(a.G, FT);
+  } else {
+    const int nfw = pl.mode == MODE_GAPPED ? pl.fhi - pl.flo + 1 : a.frames;
+    a.tps = (int)cdiv(nfw, FT);
+    a.seg_tiles = n_windows * a.tps;
+  }
+  if (pl.mode != MODE_UNSHARED && pl.gs > 0) {
+    a.gs = pl.gs;
+    a.gpt = FT / pl.gs;
+    // floats of a group's padded span, rounded up to 16 mod 32: with gs = 2 the 8 groups of a lane
+    // group's slots then fall on distinct slot pairs of the bank row, as the segment tiles' slots do
+    int gspan = (pl.gs - 1) * hop + n_fft + PADK * (pl.gs + n_fft / hop);
+    gspan = (gspan + 15) / 32 * 32 + 16;
+    a.gspan = gspan;
+    edge_tiles = cdiv(2 * n_windows, a.gpt);
+    if (a.gpt * gspan > xs) xs = a.gpt * gspan;
+  }
+  if (tail_floats > xs) xs = tail_floats;
+  a.xs_floats = (xs + 3) / 4 * 4;
+  *tiles = a.seg_tiles + edge_tiles;
+  *lds = sizeof(float) * ((size_t)a.xs_floats + 3 * (size_t)n_fft + (size_t)FT * (a.n_bins | 1));
+  if (*lds > 160 * 1024) return fail(HONK_ERR_UNSUPPORTED, "%s windows: n_fft / hop too large for the LDS plan", who);
+  if (*tiles > 0x7fffffff) return fail(HONK_ERR_UNSUPPORTED, "%s windows: too many frame tiles in one call", who);
+  return HONK_OK;
+}
+
+// host-only: make_plan for the PCEN call -- the same counts, its own workspace (the mel-range table, then
+// the E rows of the overlapping route) and stage 2's LDS plan
+static int make_pcen_plan(int64_t samples, int32_t window, int32_t stride, int32_t n_fft, int32_t hop,
+                          int32_t n_mels, int64_t first_window, int64_t n_windows, Plan* pl, int* nseg,
+                          size_t* scan_lds) {
+  if (n_mels < 1) return fail(HONK_ERR_ARG, "bad pcen arguments");
+  const int rc = make_plan(samples, window, stride, n_fft, hop, first_window, n_windows, pl);
+  if (rc != HONK_OK) return rc;
+  if (n_mels > MAX_MELS) return fail(HONK_ERR_UNSUPPORTED, "pcen windows: more than %d mel bands", MAX_MELS);
+  *nseg = SCAN_THREADS / n_mels;  // >= 2: n_mels <= 128
+  *scan_lds = sizeof(float) * ((size_t)pl->p.frames + (size_t)*nseg) * (size_t)n_mels;
+  if (*scan_lds > 160 * 1024)
+    return fail(HONK_ERR_UNSUPPORTED, "pcen windows: a window's %d x %d tile past the LDS plan", pl->p.frames,
+                n_mels);
+  if (pl->mode == MODE_OVERLAP) pl->p.workspace_bytes += pl->p.frames_computed * n_mels * (int64_t)sizeof(float);
+  return HONK_OK;
+}
+
 }  // namespace mfccs
 }  // namespace honk
 
@@ -342,49 +490,92 @@ extern "C" int honk_mfcc_windows_i16(const int16_t* pcm_i16, int64_t samples, in
   Args a;
   a.pcm = pcm_i16; a.window = window_tbl; a.melw = mel_weights; a.dct = dct; a.mrange = (const int*)workspace;
   a.out = out;
-  a.first_sample = first_window * stride;
-  a.n = n_windows;
-  a.stride = stride; a.win_len = window; a.n_fft = n_fft; a.hop = hop; a.n_bins = n_fft / 2 + 1;
-  a.n_mels = n_mels; a.n_dct = n_dct; a.frames = pl.p.frames;
-  a.flo = pl.flo; a.fhi = pl.fhi; a.mode = pl.mode; a.q = pl.q;
-  a.G = pl.p.shared_frames;
-  a.tps = 1; a.gs = 1; a.gpt = 0; a.gspan = 0;
-  int64_t edge_tiles = 0;
-  const int seg_floats = (FT - 1) * hop + n_fft + PADK * (FT + n_fft / hop);
-  int xs = seg_floats;
-  if (pl.mode == MODE_OVERLAP) {
-    a.seg_tiles = cdiv(a.G, FT);
-  } else {
-    const int nfw = pl.mode == MODE_GAPPED ? pl.fhi - pl.flo + 1 : a.frames;
-    a.tps = (int)cdiv(nfw, FT);
-    a.seg_tiles = n_windows * a.tps;
-  }
-  if (pl.mode != MODE_UNSHARED && pl.gs > 0) {
-    a.gs = pl.gs;
-    a.gpt = FT / pl.gs;
-    // floats of a group's padded span, rounded up to 16 mod 32: with gs = 2 the 8 groups of a lane
-    // group's slots then fall on distinct slot pairs of the bank row, as the segment tiles' slots do
-    int gspan = (pl.gs - 1) * hop + n_fft + PADK * (pl.gs + n_fft / hop);
-    gspan = (gspan + 15) / 32 * 32 + 16;
-    a.gspan = gspan;
-    edge_tiles = cdiv(2 * n_windows, a.gpt);
-    if (a.gpt * gspan > xs) xs = a.gpt * gspan;
-  }
+  a.n_mels = n_mels; a.n_dct = n_dct;
+  int64_t tiles;
+  size_t lds;
   // the log-mel and output tiles and the slots' destination table reuse the span area
-  const int tail_floats = FT * (n_mels + 1) + FT * (n_dct + 1) + 3 * FT;
-  if (tail_floats > xs) xs = tail_floats;
-  a.xs_floats = (xs + 3) / 4 * 4;
-  const int64_t tiles = a.seg_tiles + edge_tiles;
-  const size_t lds = sizeof(float) * ((size_t)a.xs_floats + 3 * (size_t)n_fft + (size_t)FT * (a.n_bins | 1));
-  if (lds > 160 * 1024) return fail(HONK_ERR_UNSUPPORTED, "mfcc windows: n_fft / hop too large for the LDS plan");
-  if (tiles > 0x7fffffff) return fail(HONK_ERR_UNSUPPORTED, "mfcc windows: too many frame tiles in one call");
+  const int lrc = layout(pl, "mfcc", window, stride, first_window, n_windows, n_fft, hop,
+                         FT * (n_mels + 1) + FT * (n_dct + 1) + 3 * FT, &a, &tiles, &lds);
+  if (lrc != HONK_OK) return lrc;
   hipLaunchKernelGGL(mel_range_kernel, dim3((unsigned)n_mels), dim3(64), 0, (hipStream_t)stream, mel_weights, a.n_bins,
                      (int*)workspace);
   HONK_LAUNCH_CHECK("mel_range_kernel");
   if (lds > 64 * 1024)  // (the plan's ceiling, so every shape and a captured call find it set)
-    HONK_HIP_CHECK(hipFuncSetAttribute((const void*)mfcc_windows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024));
-  hipLaunchKernelGGL(mfcc_windows_kernel, dim3((unsigned)tiles), dim3(64 * WAVES), lds, (hipStream_t)stream, a);
+    HONK_HIP_CHECK(hipFuncSetAttribute((const void*)mfcc_windows_kernel<EPI_MFCC>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL(mfcc_windows_kernel<EPI_MFCC>, dim3((unsigned)tiles), dim3(64 * WAVES), lds, (hipStream_t)stream,
+                     a);
   HONK_LAUNCH_CHECK("mfcc_windows_kernel");
+  return HONK_OK;
+}
+
+extern "C" int honk_pcen_windows_plan(int64_t samples, int32_t window, int32_t stride, int32_t n_fft, int32_t hop,
+                                      int32_t n_mels, int64_t first_window, int64_t n_windows,
+                                      honk_mfcc_windows_plan_t* plan) {
+  if (!plan) return fail(HONK_ERR_ARG, "null pointer argument");
+  mfccs::Plan pl;
+  int nseg;
+  size_t scan_lds;
+  const int rc = mfccs::make_pcen_plan(samples, window, stride, n_fft, hop, n_mels, first_window, n_windows, &pl,
+                                       &nseg, &scan_lds);
+  if (rc != HONK_OK) return rc;
+  *plan = pl.p;
+  return HONK_OK;
+}
+
+extern "C" int honk_pcen_windows_i16(const int16_t* pcm_i16, int64_t samples, int32_t window, int32_t stride,
+                                     int64_t first_window, int64_t n_windows, const float* window_tbl, int32_t n_fft,
+                                     int32_t hop, const float* mel_weights, int32_t n_mels,
+                                     const honk_pcen_params_t* params, float* out, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  using namespace mfccs;
+  Plan pl;
+  ScanArgs sa;
+  size_t scan_lds;
+  const int rc = make_pcen_plan(samples, window, stride, n_fft, hop, n_mels, first_window, n_windows, &pl, &sa.nseg,
+                                &scan_lds);
+  if (rc != HONK_OK) return rc;
+  pcen::Params p;
+  int power;
+  const int prc = pcen::check_params(params, &p, &power);
+  if (prc != HONK_OK) return prc;
+  if (n_windows == 0) return HONK_OK;
+  if (!pcm_i16 || !window_tbl || !mel_weights || !out || !workspace)
+    return fail(HONK_ERR_ARG, "null pointer argument");
+  if (workspace_bytes < (size_t)pl.p.workspace_bytes)
+    return fail(HONK_ERR_WORKSPACE, "pcen windows workspace: %zu bytes, %lld needed", workspace_bytes,
+                (long long)pl.p.workspace_bytes);
+  float* erows = (float*)((char*)workspace + 2 * MAX_MELS * sizeof(int));
+  Args a;
+  a.pcm = pcm_i16; a.window = window_tbl; a.melw = mel_weights; a.dct = nullptr; a.mrange = (const int*)workspace;
+  a.out = pl.mode == MODE_OVERLAP ? erows : out;
+  a.n_mels = n_mels; a.n_dct = 0;
+  int64_t tiles;
+  size_t lds;
+  // the E tile and the slots' row table reuse the span area
+  const int lrc = layout(pl, "pcen", window, stride, first_window, n_windows, n_fft, hop, FT * (n_mels + 1) + 2 * FT,
+                         &a, &tiles, &lds);
+  if (lrc != HONK_OK) return lrc;
+  if (n_windows > 0x7fffffff) return fail(HONK_ERR_UNSUPPORTED, "pcen windows: too many windows in one call");
+  sa.e = erows; sa.out = out; sa.G = a.G;
+  sa.frames = a.frames; sa.n_mels = n_mels; sa.flo = pl.flo; sa.fhi = pl.fhi; sa.q = pl.q; sa.mode = pl.mode;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mel_range_kernel, dim3((unsigned)n_mels), dim3(64), 0, st, mel_weights, a.n_bins,
+                     (int*)workspace);
+  HONK_LAUNCH_CHECK("mel_range_kernel");
+  const void* k1 = power == 1 ? (const void*)mfcc_windows_kernel<EPI_PCEN1>
+                              : (const void*)mfcc_windows_kernel<EPI_PCEN2>;
+  if (lds > 64 * 1024)  // (the plan's ceiling, so every shape and a captured call find it set)
+    HONK_HIP_CHECK(hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  if (power == 1)
+    hipLaunchKernelGGL(mfcc_windows_kernel<EPI_PCEN1>, dim3((unsigned)tiles), dim3(64 * WAVES), lds, st, a);
+  else
+    hipLaunchKernelGGL(mfcc_windows_kernel<EPI_PCEN2>, dim3((unsigned)tiles), dim3(64 * WAVES), lds, st, a);
+  HONK_LAUNCH_CHECK("mfcc_windows_kernel (pcen energies)");
+  if (scan_lds > 64 * 1024)
+    HONK_HIP_CHECK(hipFuncSetAttribute((const void*)pcen_windows_scan_kernel,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL(pcen_windows_scan_kernel, dim3((unsigned)n_windows), dim3(SCAN_THREADS), scan_lds, st, sa, p);
+  HONK_LAUNCH_CHECK("pcen_windows_scan_kernel");
   return HONK_OK;
 }

@@ -68,7 +68,9 @@ class TorchLabelService(LabelService):
 
     ``audio_preprocess_type`` ("MFCCs", the default, or "PCEN"): the front end the checkpoint was
     trained with (the reference's ``--audio_preprocess_type``).  PCEN restarts its smoother for every
-    window, as the reference's ``compute_pcen`` resets its transform after every clip."""
+    window, as the reference's ``compute_pcen`` resets its transform after every clip;
+    ``label_stream`` (and ``listen_stream`` / a ``StreamListener``) shares the STFT frames' mel energies
+    among the windows of a recording as the MFCC path shares its frames (``compute_pcen_windows``)."""
 
     honk_graph = False
     honk_latency = False
@@ -163,8 +165,9 @@ class TorchLabelService(LabelService):
         ``label_batch(list(stride(...)))`` with the front end on the device.  The int16 bytes are
         uploaded once; the windows go through ``compute_mfccs_windows`` (each STFT frame computed
         once), the model's forward and the softmax ``max_windows`` at a time, so memory stays
-        bounded whatever the recording's length.  Under PCEN the windows are device-side slices of
-        the uploaded recording through ``compute_pcen_batch`` (every window its own smoother)."""
+        bounded whatever the recording's length.  Under PCEN the windows go through
+        ``compute_pcen_windows``: the mel energies of each STFT frame once, then every window its own
+        smoother; no float copy of the windows is built."""
         stride_bytes = int(2 * 16000 * stride_size_ms / 1000)
         if stride_bytes < 1:
             raise ValueError("label_stream: stride_size_ms too small")
@@ -178,14 +181,12 @@ class TorchLabelService(LabelService):
             return []
         device = next(self.model.parameters()).device
         pcm = torch.from_numpy(np.frombuffer(wav_data, dtype=np.int16, count=n).copy()).to(device)
-        out, pcmf = [], None
+        out = []
         with torch.no_grad():
             for w0 in range(0, total, max_windows):
                 nw = min(max_windows, total - w0)
                 if self.audio_preprocess_type == "PCEN":
-                    if pcmf is None:
-                        pcmf = (pcm.float() * (1.0 / 32768.0)).unfold(0, 16000, stride_bytes // 2)
-                    x = self.audio_processor.compute_pcen_batch(pcmf[w0:w0 + nw].contiguous())
+                    x = self.audio_processor.compute_pcen_windows(pcm, stride_bytes // 2, 16000, w0, nw)
                 else:
                     x = self.audio_processor.compute_mfccs_windows(pcm, stride_bytes // 2, 16000, w0, nw)
                 p = F.softmax(self._net()(x).cpu(), dim=1).numpy()

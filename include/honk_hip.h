@@ -543,6 +543,44 @@ typedef struct { float eps, s, alpha, delta, r; int32_t power; } honk_pcen_param
 int honk_pcen_f32(const float* pcm, int64_t batch, int32_t samples, const float* window, int32_t n_fft,
                   int32_t hop, const float* mel_weights, int32_t n_mels,
                   const honk_pcen_params_t* params /* NULL = defaults */, float* out, void* stream);
+/*
+ * PCEN over a long recording (the /listen serving path of a PCEN-trained checkpoint): the
+ * windows of honk_mfcc_windows_i16 -- W = samples < window ? 0 : 1 + (samples - window) / stride,
+ * the range [first_window, first_window + n_windows), int16 -> x * 2^-15 -- into
+ * out [n_windows][1 + window/hop][n_mels] fp32, each window as honk_pcen_f32 would give it from
+ * its own samples: reflect padding about the window's own bounds, the smoother restarted at
+ * M[0] = E[0] of the window's own frame 0.  With stride % hop == 0 the mel energies E of a frame
+ * whose n_fft span lies inside a window are computed and stored once, whichever windows contain
+ * it; the smoother and the compression then run per window (one workgroup each).  A frame's E
+ * row is a function of its n_fft samples alone and a window's output of its E rows alone (fixed
+ * summation order, no floating-point atomics, scan segments a function of (frames, n_mels)
+ * only): ranges, chunks and shifted recordings agree bit for bit.
+ *
+ * honk_pcen_windows_plan (host-only) reports honk_mfcc_windows_plan's counts for the geometry
+ * and this call's own workspace_bytes (the mel-range table; on the overlapping shared route
+ * also frames_computed * n_mels floats of E).  honk_pcen_windows_i16 only enqueues on `stream`
+ * (three launches; no synchronisation, no allocation: capturable); n_windows is not limited to
+ * 65535.  Memory contract: the workspace's contents on entry are ignored and only
+ * [0, workspace_bytes) of the plan is touched; out is fully written and nothing outside it;
+ * pcm_i16 is never modified.
+ * Status: every refusal of honk_mfcc_windows_i16 (HONK_ERR_ARG: a null pointer, a negative
+ * count, stride < 1, window <= n_fft/2, a range past W, n_mels < 1; HONK_ERR_WORKSPACE: a short
+ * workspace; HONK_ERR_UNSUPPORTED: n_fft or hop not a multiple of 16, more than 128 mel bands, a
+ * shape past the frame kernel's LDS plan), every parameter refusal of honk_pcen_f32
+ * (HONK_ERR_ARG, the same reasons), and HONK_ERR_UNSUPPORTED where a window's
+ * [frames + 256 / n_mels][n_mels] tile is past 160 KiB of LDS -- run honk_pcen_f32 on the
+ * windows then.  The shape and the parameters are checked first; n_windows == 0: HONK_OK,
+ * nothing enqueued.
+ */
+int honk_pcen_windows_plan(int64_t samples, int32_t window, int32_t stride, int32_t n_fft, int32_t hop,
+                           int32_t n_mels, int64_t first_window, int64_t n_windows,
+                           honk_mfcc_windows_plan_t* plan);
+int honk_pcen_windows_i16(const int16_t* pcm_i16, int64_t samples, int32_t window, int32_t stride,
+                          int64_t first_window, int64_t n_windows, const float* window_tbl, int32_t n_fft,
+                          int32_t hop, const float* mel_weights, int32_t n_mels,
+                          const honk_pcen_params_t* params /* NULL = defaults */,
+                          float* out /* [n_windows][1 + window/hop][n_mels] */,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training (data-parallel train(), utils/train.py:99-135) -------------------- */
 /*
