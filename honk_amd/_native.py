@@ -46,6 +46,13 @@ class MfccWindowsPlan(ctypes.Structure):
         ("shared", ctypes.c_int32), ("frames", ctypes.c_int32)]
 
 
+class MfccSegmentsPlan(ctypes.Structure):
+    """honk_mfcc_segments_plan_t."""
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "windows", "shared_frames", "edge_frames", "frames_computed", "tiles", "workspace_bytes",
+        "table_bytes")] + [("shared", ctypes.c_int32), ("frames", ctypes.c_int32)]
+
+
 class FrontPlan(ctypes.Structure):
     """honk_front_plan_t."""
     _fields_ = [(n, ctypes.c_int32) for n in ("route", "frames", "n_bins", "launches")] + [
@@ -195,6 +202,20 @@ _PROTOS = {
                                              ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                              c_f32p, ctypes.c_int32, ctypes.c_void_p, c_f32p, ctypes.c_void_p,
                                              ctypes.c_size_t, ctypes.c_void_p]),
+    "honk_mfcc_segments_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int32] * 4
+                                + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "honk_mfcc_segments_i16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32,
+                                              c_f32p, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32,
+                                              c_f32p, ctypes.c_int32, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.c_void_p]),
+    "honk_pcen_segments_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int32] * 5
+                                + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "honk_pcen_segments_i16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32,
+                                              c_f32p, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32,
+                                              ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.c_void_p]),
     "honk_spatial_mean_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_spatial_mean_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_cross_entropy_f32": (ctypes.c_int, [c_f32p, ctypes.c_void_p, c_f32p, ctypes.c_int64, ctypes.c_int32,

@@ -329,6 +329,107 @@ class AudioPreprocessor(object):
         _native.check(rc, "honk_pcen_windows_i16")
         return out
 
+    # -- a batch of recordings of ragged length in one call (honk_mfcc_segments_i16 / honk_pcen_segments_i16) --
+    @staticmethod
+    def _segment_offsets(who, offsets, total=None, check=True):
+        off = np.asarray(offsets)
+        if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+            raise ValueError(f"{who}: offsets must be a 1-D integer sequence of n_rec + 1 entries")
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        if check and (off[0] < 0 or (np.diff(off) < 0).any() or (total is not None and off[-1] > total)):
+            raise ValueError(f"{who}: offsets must be nondecreasing within [0, {total}]")
+        return off
+
+    def _segments_plan(self, name, extra, offsets, stride, window):
+        from . import _native
+        off = self._segment_offsets(name, offsets, check=False)  # (the call itself refuses bad values)
+        n_rec = off.size - 1
+        window0 = np.zeros(n_rec + 1, np.int64)
+        table = np.zeros(6 * (n_rec + 1), np.int64)  # n_rec + 1 rows of six int64 (include/honk_hip.h)
+        plan = _native.MfccSegmentsPlan()
+        rc = getattr(_native.load(), name)(off.ctypes.data, n_rec, int(window), int(stride), self.n_fft,
+                                           self.hop_length, *extra, window0.ctypes.data, table.ctypes.data,
+                                           table.nbytes, ctypes.addressof(plan))
+        return rc, plan, window0, table
+
+    def segments_plan(self, offsets, stride, window=16000):
+        """honk_mfcc_segments_plan for this front end's n_fft / hop -> (status, MfccSegmentsPlan, window0
+        [n_rec + 1] int64, the per-recording table as an int64 array to copy to the device); host-only."""
+        return self._segments_plan("honk_mfcc_segments_plan", (), offsets, stride, window)
+
+    def pcen_segments_plan(self, offsets, stride, window=16000):
+        """honk_pcen_segments_plan: ``segments_plan`` with the PCEN call's workspace; host-only."""
+        return self._segments_plan("honk_pcen_segments_plan", (self._mel.shape[0],), offsets, stride, window)
+
+    def _compute_segments(self, which, pcm, offsets, stride, window):
+        import torch
+        from . import _native
+        who = f"compute_{which}_segments"
+        if pcm.dim() != 1 or pcm.dtype != torch.int16:
+            raise ValueError(f"{who}: pcm must be a 1-D int16 tensor")
+        stride, window = int(stride), int(window)
+        if stride < 1 or window < 1:
+            raise ValueError(f"{who}: stride >= 1, window >= 1")
+        off = self._segment_offsets(who, offsets, pcm.shape[0])
+        n_rec = off.size - 1
+        lens = np.diff(off)
+        W = np.where(lens < window, 0, 1 + (lens - window) // stride)
+        window0 = np.concatenate([[0], np.cumsum(W)]).astype(np.int64)
+        mfcc = which == "mfccs"
+        windows = self.compute_mfccs_windows if mfcc else self.compute_pcen_windows
+        frames, cols = self.n_frames(window), (self.dct_filters if mfcc else self._mel).shape[0]
+
+        def per_recording():
+            parts = [windows(pcm[off[r]:off[r + 1]], stride, window) for r in range(n_rec) if W[r]]
+            return torch.cat(parts) if parts else torch.empty(0, frames, cols, dtype=torch.float32, device=pcm.device)
+
+        if not pcm.is_cuda:
+            return per_recording(), window0
+        pcm = pcm.contiguous()
+        rc, plan, w0, table = self.segments_plan(off, stride, window) if mfcc else \
+            self.pcen_segments_plan(off, stride, window)
+        if rc == -2:  # HONK_ERR_UNSUPPORTED: a shape outside the kernel's plan
+            return per_recording(), window0
+        _native.check(rc, "honk_mfcc_segments_plan" if mfcc else "honk_pcen_segments_plan")
+        assert np.array_equal(w0, window0)
+        out = torch.empty(int(plan.windows), frames, cols, dtype=torch.float32, device=pcm.device)
+        if plan.windows == 0:
+            return out, window0
+        win, mel, dct = self._device_tables(pcm.device)
+        ws = self._windows_workspace(pcm.device, plan.workspace_bytes)
+        table_dev = torch.from_numpy(table).to(pcm.device)
+        head = (pcm.data_ptr(), pcm.shape[0], off.ctypes.data, n_rec, table_dev.data_ptr(), table.nbytes, window,
+                stride, win.data_ptr(), self.n_fft, self.hop_length, mel.data_ptr(), mel.shape[0])
+        tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_handle(pcm.device))
+        with torch.cuda.device(pcm.device):
+            if mfcc:
+                rc = _native.load().honk_mfcc_segments_i16(*head, dct.data_ptr(), cols, *tail)
+            else:
+                p = self.pcen_params
+                params = _native.PcenParams(p["eps"], p["s"], p["alpha"], p["delta"], p["r"], int(p["power"]))
+                rc = _native.load().honk_pcen_segments_i16(*head, ctypes.addressof(params), *tail)
+        if rc == -2:
+            return per_recording(), window0
+        _native.check(rc, "honk_mfcc_segments_i16" if mfcc else "honk_pcen_segments_i16")
+        return out, window0
+
+    def compute_mfccs_segments(self, pcm, offsets, stride, window=16000):
+        """pcm: 1-D int16 torch tensor holding a batch of recordings, recording r being
+        ``pcm[offsets[r]:offsets[r + 1]]`` (offsets: n_rec + 1 nondecreasing ints within the tensor)
+        -> (x [sum W_r, frames, n_dct] float32, window0 [n_rec + 1] int64): recording r's rows
+        ``x[window0[r]:window0[r + 1]]`` are ``compute_mfccs_windows`` of that recording alone, bit for bit.
+
+        ROCm device: one plan, one upload of the per-recording table and one honk_mfcc_segments_i16
+        (csrc/mfcc_stream.hip), whatever the number of recordings; a shape the call refuses as unsupported
+        goes through ``compute_mfccs_windows`` per recording.  CPU: ``compute_mfccs_windows`` per
+        recording.  A bad ``offsets`` raises ValueError."""
+        return self._compute_segments("mfccs", pcm, offsets, stride, window)
+
+    def compute_pcen_segments(self, pcm, offsets, stride, window=16000):
+        """``compute_mfccs_segments`` under PCEN (``self.pcen_params``; honk_pcen_segments_i16):
+        recording r's rows are ``compute_pcen_windows`` of that recording alone, bit for bit."""
+        return self._compute_segments("pcen", pcm, offsets, stride, window)
+
     def _windows_workspace(self, device, nbytes):
         import torch
         key = str(device)

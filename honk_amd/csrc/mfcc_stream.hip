@@ -33,6 +33,17 @@
 // E[0] of the window's own reflected frame 0: the smoother restarts per window) and writes
 // the window's rows of out once; the whole tile is read before any of it is written, so the
 // in-place routes are safe.
+//
+// A batch of recordings of ragged length (honk_mfcc_segments_i16 / honk_pcen_segments_i16): the same
+// kernels (SEG) over recordings concatenated in one buffer and located by offsets [n_rec + 1].  One
+// route for the batch; the segment tiles of each recording laid out as above for that recording
+// alone, in recording order; the edge tiles over the batch's global window index, so one edge tile
+// holds windows of several recordings.  A workgroup (in an edge tile: each group) finds its recording
+// by binary search over a per-recording table in device memory (struct Rec; filled on the host by the
+// plan call), once, before staging, and keeps its groups in LDS.  out [sum W_r][frames][n_dct]: a
+// recording's rows are, bit for bit, the single-recording call's -- the per-frame arithmetic is the
+// same code.  PCEN: [sum G_r][n_mels] shared rows, then [sum W_r][head + tail][n_mels] edge rows in
+// the workspace; stage 2 one workgroup per global window.
 #include "common.h"
 #include "pcen_scan.h"
 
@@ -53,6 +64,18 @@ enum { MODE_UNSHARED = 0, MODE_OVERLAP = 1, MODE_GAPPED = 2 };
 // energies of |X| (power 1) / |X|^2 (power 2), each frame's row stored once
 enum { EPI_MFCC = 0, EPI_PCEN1 = 1, EPI_PCEN2 = 2 };
 
+// one row of the per-recording table of the batched calls (honk_*_segments_i16): filled on the host by
+// the plan call, read on the device.  Row n_rec is a sentinel holding the totals, so the last r with
+// tile0[r] <= t (window0[r] <= w) is the recording of tile t (window w) and never an empty one
+struct Rec {
+  int64_t tile0;    // first segment tile
+  int64_t window0;  // first window: row of out
+  int64_t srow0;    // first shared-frame row (MODE_OVERLAP)
+  int64_t sample0;  // offsets[r]
+  int64_t n;        // windows
+  int64_t G;        // MODE_OVERLAP: shared frames
+};
+
 struct Args {
   const int16_t* pcm;
   const float* window;  // [n_fft]
@@ -70,13 +93,18 @@ struct Args {
   int tps;       // per-window modes: segment tiles per window
   int gs, gpt, gspan;  // edge tiles: slots per group, groups per tile, LDS floats per group
   int xs_floats;
+  // a batch of recordings (SEG kernels): n, G and seg_tiles are the batch's totals, first_sample is unused
+  const Rec* table;  // [n_rec + 1]
+  int64_t n_rec;
 };
 
 struct Group {
   int64_t base;  // sample of the (virtual) window's start
   int64_t L;     // its length: reflection bound
-  int64_t wl;    // window (relative to the range) of slot 0; MODE_OVERLAP: unused
+  int64_t wl;    // window (row block of out) of slot 0; MODE_OVERLAP segments: of the recording's first
   int64_t f0;    // frame of slot 0
+  int64_t n;     // windows of the group's recording
+  int64_t srow;  // MODE_OVERLAP: the recording's first shared-frame row
   int nf;        // frames (0: an empty group)
 };
 
@@ -87,32 +115,66 @@ __device__ __forceinline__ int64_t reflect(int64_t i, int64_t n) {
   return i;
 }
 
+// the last row r < n_rec of the table with tile0 (BY_TILE) / window0 <= v: log2(n_rec) steps
+template <bool BY_TILE>
+__device__ __forceinline__ const Rec& rec_of(const Rec* table, int64_t n_rec, int64_t v) {
+  int64_t lo = 0, hi = n_rec;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((BY_TILE ? table[mid].tile0 : table[mid].window0) <= v)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return table[lo > 0 ? lo - 1 : 0];
+}
+
+template <bool SEG>
 __device__ __forceinline__ Group group_of(const Args& a, int64_t t, int gi) {
   Group g;
   if (t < a.seg_tiles) {
+    int64_t first = a.first_sample, n = a.n, G = a.G, w0 = 0, tl = t;
+    g.srow = 0;
+    if constexpr (SEG) {
+      const Rec& r = rec_of<true>(a.table, a.n_rec, t);
+      first = r.sample0; n = r.n; G = r.G; w0 = r.window0; tl = t - r.tile0;
+      g.srow = r.srow0;
+    }
+    g.n = n;
     if (a.mode == MODE_OVERLAP) {
-      g.base = a.first_sample;
-      g.L = (a.n - 1) * a.stride + a.win_len;
-      g.wl = 0;
-      g.f0 = a.flo + t * FT;
-      g.nf = (int)min((int64_t)FT, a.G - t * FT);
+      g.base = first;
+      g.L = (n - 1) * a.stride + a.win_len;
+      g.wl = w0;
+      g.f0 = a.flo + tl * FT;
+      g.nf = (int)min((int64_t)FT, G - tl * FT);
     } else {
       const int fa = a.mode == MODE_GAPPED ? a.flo : 0;
       const int fb = a.mode == MODE_GAPPED ? a.fhi + 1 : a.frames;
-      g.wl = t / a.tps;
-      g.base = a.first_sample + g.wl * a.stride;
+      const int64_t w = tl / a.tps;
+      g.wl = w0 + w;
+      g.base = first + w * a.stride;
       g.L = a.win_len;
-      g.f0 = fa + (int)(t % a.tps) * FT;
+      g.f0 = fa + (int)(tl % a.tps) * FT;
       g.nf = min(FT, fb - (int)g.f0);
     }
   } else {
     const int64_t gid = (t - a.seg_tiles) * a.gpt + gi;
     g.wl = gid >> 1;
+    g.n = a.n;
+    g.srow = 0;
+    const bool live = g.wl < a.n && gi < a.gpt;
     g.base = a.first_sample + g.wl * a.stride;
+    if constexpr (SEG) {
+      g.base = 0;
+      if (live) {
+        const Rec& r = rec_of<false>(a.table, a.n_rec, g.wl);
+        g.base = r.sample0 + (g.wl - r.window0) * a.stride;
+      }
+    }
     g.L = a.win_len;
     const bool tail = gid & 1;
     g.f0 = tail ? a.fhi + 1 : 0;
-    g.nf = (g.wl < a.n && gi < a.gpt) ? (tail ? a.frames - 1 - a.fhi : a.flo) : 0;
+    g.nf = live ? (tail ? a.frames - 1 - a.fhi : a.flo) : 0;
   }
   return g;
 }
@@ -137,7 +199,9 @@ __global__ __launch_bounds__(64) void mel_range_kernel(const float* melw, int n_
   }
 }
 
-template <int EPI>
+// SEG: a batch of recordings -- every group finds its recording in a.table once (one lane per group,
+// the groups kept in LDS behind the power tile), before staging
+template <int EPI, bool SEG = false>
 __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int N = a.n_fft, NB = a.n_bins, NM = a.n_mels, ND = a.n_dct, hop = a.hop, pad = N / 2;
@@ -154,9 +218,20 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
   const bool edge = t >= a.seg_tiles;
   const int gs = edge ? a.gs : FT, ng = edge ? a.gpt : 1, gspan = edge ? a.gspan : 0;
   const int glen = (gs - 1) * hop + N;
+  Group* grp = (Group*)(pw + FT * PS);  // [ng] (SEG; 8-byte aligned: every term before it is even)
+  if constexpr (SEG) {
+    if (tid < ng) grp[tid] = group_of<true>(a, t, tid);
+    __syncthreads();
+  }
+  const auto group = [&](int gi) -> Group {
+    if constexpr (SEG)
+      return grp[gi];
+    else
+      return group_of<false>(a, t, gi);
+  };
 
   for (int gi = 0; gi < ng; ++gi) {
-    const Group gr = group_of(a, t, gi);
+    const Group gr = group(gi);
     const int have = gr.nf > 0 ? (gr.nf - 1) * hop + N : 0;
     const int64_t off0 = gr.f0 * hop - pad;
     float* xg = xs + gi * gspan;
@@ -246,12 +321,12 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
       const int gi = tid / gs, fi = tid - gi * gs;
       int64_t row = -1;
       if (gi < ng) {
-        const Group gr = group_of(a, t, gi);
+        const Group gr = group(gi);
         if (fi < gr.nf) {
           if (a.mode != MODE_OVERLAP)
             row = gr.wl * a.frames + gr.f0 + fi;
           else if (!edge)
-            row = gr.f0 - a.flo + fi;
+            row = gr.srow + gr.f0 - a.flo + fi;
           else
             row = a.G + gr.wl * (a.flo + a.frames - 1 - a.fhi) + (gr.f0 > a.fhi ? a.flo : 0) + fi;
         }
@@ -291,13 +366,13 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
     int64_t row = 0;
     int cnt = 0;
     if (gi < ng) {
-      const Group gr = group_of(a, t, gi);
+      const Group gr = group(gi);
       if (fi < gr.nf) {
         if (fan) {
           const int64_t jl = gr.f0 + fi;  // frame of the virtual window: frame jl - w q of window w
           const int64_t wlo = jl > a.fhi ? (jl - a.fhi + a.q - 1) / a.q : 0;
-          const int64_t whi = min(a.n - 1, (jl - a.flo) / a.q);
-          row = wlo * a.frames + (jl - wlo * a.q);
+          const int64_t whi = min(gr.n - 1, (jl - a.flo) / a.q);
+          row = (gr.wl + wlo) * a.frames + (jl - wlo * a.q);
           cnt = (int)(whi - wlo + 1);
         } else {
           row = gr.wl * a.frames + gr.f0 + fi;
@@ -327,6 +402,8 @@ struct ScanArgs {
   float* out;      // [n][frames][n_mels]
   int64_t G;
   int frames, n_mels, flo, fhi, q, mode, nseg;
+  const Rec* table;  // a batch of recordings: G is the batch's total, w the global window; else null
+  int64_t n_rec;
 };
 
 // one workgroup per window: E tile -> LDS, smoother + compression there, the window's rows out
@@ -337,7 +414,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void pcen_windows_scan_kernel(ScanArg
   float* o = s.out + w * F * NM;
   if (s.mode == MODE_OVERLAP) {
     const int ne = s.flo + F - 1 - s.fhi;
-    const int64_t erow = s.G + w * ne, srow = w * s.q - s.flo;
+    int64_t srow = w * s.q - s.flo;
+    if (s.table) {
+      const Rec& r = rec_of<false>(s.table, s.n_rec, w);
+      srow = r.srow0 + (w - r.window0) * s.q - s.flo;
+    }
+    const int64_t erow = s.G + w * ne;
     for (int i = threadIdx.x; i < F * NM; i += blockDim.x) {
       const int f = i / NM, m = i - f * NM;
       const int64_t row = f < s.flo ? erow + f : (f > s.fhi ? erow + s.flo + (f - s.fhi - 1) : srow + f);
@@ -407,6 +489,7 @@ static int layout(const Plan& pl, const char* who, int32_t window, int32_t strid
   a.flo = pl.flo; a.fhi = pl.fhi; a.mode = pl.mode; a.q = pl.q;
   a.G = pl.p.shared_frames;
   a.tps = 1; a.gs = 1; a.gpt = 0; a.gspan = 0;
+  a.table = nullptr; a.n_rec = 0;
   int64_t edge_tiles = 0;
   const int seg_floats = (FT - 1) * hop + n_fft + PADK * (FT + n_fft / hop);
   int xs = seg_floats;
@@ -452,6 +535,84 @@ static int make_pcen_plan(int64_t samples, int32_t window, int32_t stride, int32
     return fail(HONK_ERR_UNSUPPORTED, "pcen windows: a window's %d x %d tile past the LDS plan", pl->p.frames,
                 n_mels);
   if (pl->mode == MODE_OVERLAP) pl->p.workspace_bytes += pl->p.frames_computed * n_mels * (int64_t)sizeof(float);
+  return HONK_OK;
+}
+
+// ---- a batch of recordings ------------------------------------------------------------ //
+struct SegPlan {
+  honk_mfcc_segments_plan_t p;
+  int64_t seg_tiles;  // sum over the recordings; the edge tiles (over the batch's windows) follow
+};
+
+// host-only: the batch's counts, window0 and the table from the offsets.  geo: make_plan's (make_pcen_plan's)
+// route of the geometry, taken on a recording without windows; check_total: offsets[n_rec] against
+// total_samples (the _i16 calls); e_floats: floats of E per computed frame the workspace holds (PCEN on
+// the overlapping route, else 0)
+static int make_segments_plan(const Plan& geo, const char* who, const int64_t* offsets, int64_t n_rec,
+                              bool check_total, int64_t total_samples, int32_t window, int32_t stride,
+                              int64_t e_floats, int64_t* window0, Rec* table, size_t table_capacity, SegPlan* sp) {
+  if (n_rec < 0 || (check_total && total_samples < 0)) return fail(HONK_ERR_ARG, "negative count");
+  if (!offsets) return fail(HONK_ERR_ARG, "null pointer argument");
+  if (offsets[0] < 0) return fail(HONK_ERR_ARG, "%s segments: negative offset", who);
+  for (int64_t r = 0; r < n_rec; ++r)
+    if (offsets[r + 1] < offsets[r]) return fail(HONK_ERR_ARG, "%s segments: offsets decrease at recording %lld", who, (long long)r);
+  if (check_total && offsets[n_rec] > total_samples)
+    return fail(HONK_ERR_ARG, "%s segments: offsets run past the %lld samples", who, (long long)total_samples);
+  honk_mfcc_segments_plan_t& p = sp->p;
+  p = honk_mfcc_segments_plan_t{};
+  p.frames = geo.p.frames;
+  p.shared = geo.p.shared;
+  p.table_bytes = (n_rec + 1) * (int64_t)sizeof(Rec);
+  if (table && table_capacity < (size_t)p.table_bytes)
+    return fail(HONK_ERR_WORKSPACE, "%s segments table: %zu bytes, %lld needed", who, table_capacity,
+                (long long)p.table_bytes);
+  const int nint = geo.fhi - geo.flo + 1;
+  const int nfw = geo.mode == MODE_GAPPED ? nint : p.frames;  // per-window routes: segment frames of a window
+  const int64_t tps = cdiv(nfw, FT);
+  int64_t tiles = 0, windows = 0, srow = 0;
+  for (int64_t r = 0; r < n_rec; ++r) {
+    const int64_t len = offsets[r + 1] - offsets[r];
+    const int64_t W = len < window ? 0 : 1 + (len - window) / stride;
+    const int64_t G = geo.mode == MODE_OVERLAP && W > 0 ? (W - 1) * geo.q + nint : 0;
+    if (window0) window0[r] = windows;
+    if (table) table[r] = Rec{tiles, windows, srow, offsets[r], W, G};
+    if (geo.mode == MODE_UNSHARED) {
+      p.frames_computed += W * p.frames;
+    } else {
+      const int64_t shared = geo.mode == MODE_OVERLAP ? G : W * nint;
+      p.shared_frames += shared;
+      p.edge_frames += W * (p.frames - nint);
+      srow += shared;
+    }
+    tiles += geo.mode == MODE_OVERLAP ? cdiv(G, FT) : W * tps;
+    windows += W;
+  }
+  if (geo.mode != MODE_UNSHARED) p.frames_computed = p.shared_frames + p.edge_frames;
+  if (window0) window0[n_rec] = windows;
+  if (table) table[n_rec] = Rec{tiles, windows, srow, offsets[n_rec], 0, 0};
+  sp->seg_tiles = tiles;
+  if (geo.mode != MODE_UNSHARED && geo.gs > 0) tiles += cdiv(2 * windows, FT / geo.gs);
+  p.windows = windows;
+  p.tiles = tiles;
+  p.workspace_bytes = 2 * MAX_MELS * (int64_t)sizeof(int) + p.frames_computed * e_floats * (int64_t)sizeof(float);
+  if (tiles > 0x7fffffff) return fail(HONK_ERR_UNSUPPORTED, "%s segments: too many frame tiles in one call", who);
+  return HONK_OK;
+}
+
+// host-only: layout()'s shape fields and LDS plan for the batch (the groups' table behind the power tile)
+static int segments_layout(const Plan& geo, const SegPlan& sp, const char* who, int32_t window, int32_t stride,
+                           int32_t n_fft, int32_t hop, int tail_floats, const void* table_dev, int64_t n_rec,
+                           Args* ap, size_t* lds) {
+  int64_t none;
+  const int rc = layout(geo, who, window, stride, 0, 0, n_fft, hop, tail_floats, ap, &none, lds);
+  if (rc != HONK_OK) return rc;
+  ap->n = sp.p.windows;
+  ap->G = sp.p.shared_frames;
+  ap->seg_tiles = sp.seg_tiles;
+  ap->table = (const Rec*)table_dev;
+  ap->n_rec = n_rec;
+  *lds += FT * sizeof(Group);
+  if (*lds > 160 * 1024) return fail(HONK_ERR_UNSUPPORTED, "%s segments: n_fft / hop too large for the LDS plan", who);
   return HONK_OK;
 }
 
@@ -557,7 +718,7 @@ extern "C" int honk_pcen_windows_i16(const int16_t* pcm_i16, int64_t samples, in
                          &a, &tiles, &lds);
   if (lrc != HONK_OK) return lrc;
   if (n_windows > 0x7fffffff) return fail(HONK_ERR_UNSUPPORTED, "pcen windows: too many windows in one call");
-  sa.e = erows; sa.out = out; sa.G = a.G;
+  sa.e = erows; sa.out = out; sa.G = a.G; sa.table = nullptr; sa.n_rec = 0;
   sa.frames = a.frames; sa.n_mels = n_mels; sa.flo = pl.flo; sa.fhi = pl.fhi; sa.q = pl.q; sa.mode = pl.mode;
   const hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mel_range_kernel, dim3((unsigned)n_mels), dim3(64), 0, st, mel_weights, a.n_bins,
@@ -576,6 +737,145 @@ extern "C" int honk_pcen_windows_i16(const int16_t* pcm_i16, int64_t samples, in
     HONK_HIP_CHECK(hipFuncSetAttribute((const void*)pcen_windows_scan_kernel,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   hipLaunchKernelGGL(pcen_windows_scan_kernel, dim3((unsigned)n_windows), dim3(SCAN_THREADS), scan_lds, st, sa, p);
+  HONK_LAUNCH_CHECK("pcen_windows_scan_kernel");
+  return HONK_OK;
+}
+
+extern "C" int honk_mfcc_segments_plan(const int64_t* offsets, int64_t n_rec, int32_t window, int32_t stride,
+                                       int32_t n_fft, int32_t hop, int64_t* window0, void* table,
+                                       size_t table_capacity, honk_mfcc_segments_plan_t* plan) {
+  using namespace mfccs;
+  if (!plan) return fail(HONK_ERR_ARG, "null pointer argument");
+  Plan geo;
+  const int rc = make_plan(0, window, stride, n_fft, hop, 0, 0, &geo);
+  if (rc != HONK_OK) return rc;
+  SegPlan sp;
+  const int src = make_segments_plan(geo, "mfcc", offsets, n_rec, false, 0, window, stride, 0, window0, (Rec*)table,
+                                     table_capacity, &sp);
+  if (src != HONK_OK) return src;
+  *plan = sp.p;
+  return HONK_OK;
+}
+
+extern "C" int honk_mfcc_segments_i16(const int16_t* pcm_i16, int64_t total_samples, const int64_t* offsets,
+                                      int64_t n_rec, const void* table_dev, size_t table_bytes, int32_t window,
+                                      int32_t stride, const float* window_tbl, int32_t n_fft, int32_t hop,
+                                      const float* mel_weights, int32_t n_mels, const float* dct, int32_t n_dct,
+                                      float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace mfccs;
+  if (n_mels < 1 || n_dct < 1) return fail(HONK_ERR_ARG, "bad mfcc arguments");
+  Plan geo;
+  const int rc = make_plan(0, window, stride, n_fft, hop, 0, 0, &geo);
+  if (rc != HONK_OK) return rc;
+  SegPlan sp;
+  const int src = make_segments_plan(geo, "mfcc", offsets, n_rec, true, total_samples, window, stride, 0, nullptr,
+                                     nullptr, 0, &sp);
+  if (src != HONK_OK) return src;
+  if (sp.p.windows == 0) return HONK_OK;
+  if (!pcm_i16 || !table_dev || !window_tbl || !mel_weights || !dct || !out || !workspace)
+    return fail(HONK_ERR_ARG, "null pointer argument");
+  if (n_mels > MAX_MELS) return fail(HONK_ERR_UNSUPPORTED, "mfcc segments: more than %d mel bands", MAX_MELS);
+  if (workspace_bytes < (size_t)sp.p.workspace_bytes)
+    return fail(HONK_ERR_WORKSPACE, "mfcc segments workspace: %zu bytes, %lld needed", workspace_bytes,
+                (long long)sp.p.workspace_bytes);
+  if (table_bytes < (size_t)sp.p.table_bytes)
+    return fail(HONK_ERR_WORKSPACE, "mfcc segments table: %zu bytes, %lld needed", table_bytes,
+                (long long)sp.p.table_bytes);
+  Args a;
+  a.pcm = pcm_i16; a.window = window_tbl; a.melw = mel_weights; a.dct = dct; a.mrange = (const int*)workspace;
+  a.out = out;
+  a.n_mels = n_mels; a.n_dct = n_dct;
+  size_t lds;
+  const int lrc = segments_layout(geo, sp, "mfcc", window, stride, n_fft, hop,
+                                  FT * (n_mels + 1) + FT * (n_dct + 1) + 3 * FT, table_dev, n_rec, &a, &lds);
+  if (lrc != HONK_OK) return lrc;
+  hipLaunchKernelGGL(mel_range_kernel, dim3((unsigned)n_mels), dim3(64), 0, (hipStream_t)stream, mel_weights, a.n_bins,
+                     (int*)workspace);
+  HONK_LAUNCH_CHECK("mel_range_kernel");
+  if (lds > 64 * 1024)
+    HONK_HIP_CHECK(hipFuncSetAttribute((const void*)mfcc_windows_kernel<EPI_MFCC, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL((mfcc_windows_kernel<EPI_MFCC, true>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds,
+                     (hipStream_t)stream, a);
+  HONK_LAUNCH_CHECK("mfcc_windows_kernel (segments)");
+  return HONK_OK;
+}
+
+extern "C" int honk_pcen_segments_plan(const int64_t* offsets, int64_t n_rec, int32_t window, int32_t stride,
+                                       int32_t n_fft, int32_t hop, int32_t n_mels, int64_t* window0, void* table,
+                                       size_t table_capacity, honk_mfcc_segments_plan_t* plan) {
+  using namespace mfccs;
+  if (!plan) return fail(HONK_ERR_ARG, "null pointer argument");
+  Plan geo;
+  int nseg;
+  size_t scan_lds;
+  const int rc = make_pcen_plan(0, window, stride, n_fft, hop, n_mels, 0, 0, &geo, &nseg, &scan_lds);
+  if (rc != HONK_OK) return rc;
+  SegPlan sp;
+  const int src = make_segments_plan(geo, "pcen", offsets, n_rec, false, 0, window, stride,
+                                     geo.mode == MODE_OVERLAP ? n_mels : 0, window0, (Rec*)table, table_capacity, &sp);
+  if (src != HONK_OK) return src;
+  *plan = sp.p;
+  return HONK_OK;
+}
+
+extern "C" int honk_pcen_segments_i16(const int16_t* pcm_i16, int64_t total_samples, const int64_t* offsets,
+                                      int64_t n_rec, const void* table_dev, size_t table_bytes, int32_t window,
+                                      int32_t stride, const float* window_tbl, int32_t n_fft, int32_t hop,
+                                      const float* mel_weights, int32_t n_mels, const honk_pcen_params_t* params,
+                                      float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace mfccs;
+  Plan geo;
+  ScanArgs sa;
+  size_t scan_lds;
+  const int rc = make_pcen_plan(0, window, stride, n_fft, hop, n_mels, 0, 0, &geo, &sa.nseg, &scan_lds);
+  if (rc != HONK_OK) return rc;
+  pcen::Params p;
+  int power;
+  const int prc = pcen::check_params(params, &p, &power);
+  if (prc != HONK_OK) return prc;
+  SegPlan sp;
+  const int src = make_segments_plan(geo, "pcen", offsets, n_rec, true, total_samples, window, stride,
+                                     geo.mode == MODE_OVERLAP ? n_mels : 0, nullptr, nullptr, 0, &sp);
+  if (src != HONK_OK) return src;
+  if (sp.p.windows == 0) return HONK_OK;
+  if (!pcm_i16 || !table_dev || !window_tbl || !mel_weights || !out || !workspace)
+    return fail(HONK_ERR_ARG, "null pointer argument");
+  if (workspace_bytes < (size_t)sp.p.workspace_bytes)
+    return fail(HONK_ERR_WORKSPACE, "pcen segments workspace: %zu bytes, %lld needed", workspace_bytes,
+                (long long)sp.p.workspace_bytes);
+  if (table_bytes < (size_t)sp.p.table_bytes)
+    return fail(HONK_ERR_WORKSPACE, "pcen segments table: %zu bytes, %lld needed", table_bytes,
+                (long long)sp.p.table_bytes);
+  float* erows = (float*)((char*)workspace + 2 * MAX_MELS * sizeof(int));
+  Args a;
+  a.pcm = pcm_i16; a.window = window_tbl; a.melw = mel_weights; a.dct = nullptr; a.mrange = (const int*)workspace;
+  a.out = geo.mode == MODE_OVERLAP ? erows : out;
+  a.n_mels = n_mels; a.n_dct = 0;
+  size_t lds;
+  const int lrc = segments_layout(geo, sp, "pcen", window, stride, n_fft, hop, FT * (n_mels + 1) + 2 * FT, table_dev,
+                                  n_rec, &a, &lds);
+  if (lrc != HONK_OK) return lrc;
+  if (sp.p.windows > 0x7fffffff) return fail(HONK_ERR_UNSUPPORTED, "pcen segments: too many windows in one call");
+  sa.e = erows; sa.out = out; sa.G = a.G; sa.table = (const Rec*)table_dev; sa.n_rec = n_rec;
+  sa.frames = a.frames; sa.n_mels = n_mels; sa.flo = geo.flo; sa.fhi = geo.fhi; sa.q = geo.q; sa.mode = geo.mode;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mel_range_kernel, dim3((unsigned)n_mels), dim3(64), 0, st, mel_weights, a.n_bins,
+                     (int*)workspace);
+  HONK_LAUNCH_CHECK("mel_range_kernel");
+  const void* k1 = power == 1 ? (const void*)mfcc_windows_kernel<EPI_PCEN1, true>
+                              : (const void*)mfcc_windows_kernel<EPI_PCEN2, true>;
+  if (lds > 64 * 1024)
+    HONK_HIP_CHECK(hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  if (power == 1)
+    hipLaunchKernelGGL((mfcc_windows_kernel<EPI_PCEN1, true>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds, st, a);
+  else
+    hipLaunchKernelGGL((mfcc_windows_kernel<EPI_PCEN2, true>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds, st, a);
+  HONK_LAUNCH_CHECK("mfcc_windows_kernel (segments, pcen energies)");
+  if (scan_lds > 64 * 1024)
+    HONK_HIP_CHECK(hipFuncSetAttribute((const void*)pcen_windows_scan_kernel,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL(pcen_windows_scan_kernel, dim3((unsigned)sp.p.windows), dim3(SCAN_THREADS), scan_lds, st, sa, p);
   HONK_LAUNCH_CHECK("pcen_windows_scan_kernel");
   return HONK_OK;
 }

@@ -70,7 +70,10 @@ class TorchLabelService(LabelService):
     trained with (the reference's ``--audio_preprocess_type``).  PCEN restarts its smoother for every
     window, as the reference's ``compute_pcen`` resets its transform after every clip;
     ``label_stream`` (and ``listen_stream`` / a ``StreamListener``) shares the STFT frames' mel energies
-    among the windows of a recording as the MFCC path shares its frames (``compute_pcen_windows``)."""
+    among the windows of a recording as the MFCC path shares its frames (``compute_pcen_windows``).
+
+    Many recordings at once: ``label_streams`` (one upload, one ragged-batch front-end call, one forward
+    and one download per batch of windows) and a ``StreamPool`` over it, under either front end."""
 
     honk_graph = False
     honk_latency = False
@@ -193,6 +196,51 @@ class TorchLabelService(LabelService):
                 out.extend((self.labels[int(np.argmax(r))], float(np.max(r))) for r in p)
         return out
 
+    def label_streams(self, recordings, stride_size_ms=500, max_windows=8192):
+        """``[label_stream(r, stride_size_ms) for r in recordings]`` (int16 byte strings) with the whole
+        batch in one front-end call: the bytes are concatenated and uploaded once; the recordings go, in
+        order, in batches of at most ``max_windows`` windows through ``compute_mfccs_segments``
+        (``compute_pcen_segments`` under PCEN), one forward, one softmax and one download per batch.  A
+        recording with more than ``max_windows`` windows goes through ``label_stream`` itself.  On the
+        CPU, or with an odd stride in bytes, it is ``label_stream`` per recording."""
+        stride_bytes = int(2 * 16000 * stride_size_ms / 1000)
+        if stride_bytes < 1:
+            raise ValueError("label_streams: stride_size_ms too small")
+        if self.no_cuda or stride_bytes % 2:
+            return [self.label_stream(r, stride_size_ms, max_windows) for r in recordings]
+        if max_windows < 1:
+            raise ValueError("label_streams: max_windows >= 1")
+        step = stride_bytes // 2
+        ns = [len(r) // 2 for r in recordings]
+        Ws = [0 if n < 16000 else 1 + (n - 16000) // step for n in ns]
+        out = [[] for _ in recordings]
+        batched = [i for i, w in enumerate(Ws) if 0 < w <= max_windows]
+        for i, w in enumerate(Ws):
+            if w > max_windows:
+                out[i] = self.label_stream(recordings[i], stride_size_ms, max_windows)
+        if not batched:
+            return out
+        device = next(self.model.parameters()).device
+        off = np.concatenate([[0], np.cumsum([ns[i] for i in batched])]).astype(np.int64)
+        pcm = torch.from_numpy(np.concatenate([np.frombuffer(recordings[i], dtype=np.int16, count=ns[i])
+                                               for i in batched])).to(device)
+        segments = self.audio_processor.compute_pcen_segments if self.audio_preprocess_type == "PCEN" else \
+            self.audio_processor.compute_mfccs_segments
+        with torch.no_grad():
+            a = 0
+            while a < len(batched):
+                b, nw = a, 0
+                while b < len(batched) and nw + Ws[batched[b]] <= max_windows:
+                    nw += Ws[batched[b]]
+                    b += 1
+                x, w0 = segments(pcm, off[a:b + 1], step, 16000)
+                p = F.softmax(self._net()(x).cpu(), dim=1).numpy()
+                for j in range(a, b):
+                    out[batched[j]] = [(self.labels[int(np.argmax(r))], float(np.max(r)))
+                                       for r in p[w0[j - a]:w0[j - a + 1]]]
+                a = b
+        return out
+
     def listen_stream(self, wav_data, stride_size_ms=500, method="labels", keyword="command", min_keyword_prob=0.85):
         """``listen`` over ``label_stream``: the same return contract and early-exit order."""
         labels = {}
@@ -217,21 +265,68 @@ class StreamListener(object):
         self._buf = b""
         self._skip = 0  # bytes before the next window's start still to come (stride > window)
 
-    def feed(self, wav_bytes):
+    def _push(self, wav_bytes):
+        """Take in a chunk -> the buffer whose whole windows are to be labelled now, or None while it holds
+        less than one window.  The window arithmetic of ``feed`` (and of a ``StreamPool``'s streams)."""
         wav_bytes = bytes(wav_bytes)
         if self._skip:
             drop = min(self._skip, len(wav_bytes))
             self._skip -= drop
             wav_bytes = wav_bytes[drop:]
         self._buf += wav_bytes
-        if len(self._buf) < self._window:
-            return []
+        return self._buf if len(self._buf) >= self._window else None
+
+    def _pop(self, labelled):
+        """Drop what the ``labelled`` windows of the buffer ``_push`` returned have consumed."""
         done = 1 + (len(self._buf) - self._window) // self._stride
-        out = self.service.label_stream(self._buf, self.stride_size_ms)
-        assert len(out) == done
+        assert labelled == done
         nxt = done * self._stride
         self._skip = max(0, nxt - len(self._buf))
         self._buf = self._buf[nxt:]
+
+    def feed(self, wav_bytes):
+        buf = self._push(wav_bytes)
+        if buf is None:
+            return []
+        out = self.service.label_stream(buf, self.stride_size_ms)
+        self._pop(len(out))
+        return out
+
+
+class StreamPool(object):
+    """Many ``StreamListener``s on one service, labelled together: ``feed({key: wav_bytes, ...})`` returns
+    ``{key: [(label, prob), ...]}`` for every key fed -- per key, over any sequence of ticks, what a
+    ``StreamListener`` fed the same bytes returns.  A key is opened at its first feed; ``close(key)`` drops
+    its tail.  Per tick the streams that complete at least one window go through ONE
+    ``service.label_streams`` call (one upload, one front-end call, one forward, one download), whatever
+    their number.  Tails stay on the host, as a ``StreamListener``'s."""
+
+    def __init__(self, service, stride_size_ms=500):
+        self.service = service
+        self.stride_size_ms = stride_size_ms
+        self._streams = {}
+
+    def keys(self):
+        return list(self._streams)
+
+    def close(self, key):
+        self._streams.pop(key, None)
+
+    def feed(self, chunks):
+        out, ready = {}, []
+        for key, wav_bytes in chunks.items():
+            sl = self._streams.get(key)
+            if sl is None:
+                sl = self._streams[key] = StreamListener(self.service, self.stride_size_ms)
+            out[key] = []
+            buf = sl._push(wav_bytes)
+            if buf is not None:
+                ready.append((key, sl, buf))
+        if ready:
+            labelled = self.service.label_streams([buf for _, _, buf in ready], self.stride_size_ms)
+            for (key, sl, _), got in zip(ready, labelled):
+                sl._pop(len(got))
+                out[key] = got
         return out
 
 

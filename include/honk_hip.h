@@ -581,6 +581,78 @@ int honk_pcen_windows_i16(const int16_t* pcm_i16, int64_t samples, int32_t windo
                           const honk_pcen_params_t* params /* NULL = defaults */,
                           float* out /* [n_windows][1 + window/hop][n_mels] */,
                           void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * The two calls above over a batch of recordings of ragged length in ONE call (a server that
+ * listens to many streams at once: one front-end call, one forward and one download per tick).
+ * The recordings lie in one device buffer pcm_i16 [total_samples]; the host array
+ * offsets [n_rec + 1] (nondecreasing, 0 <= offsets[0], offsets[n_rec] <= total_samples) locates
+ * them: recording r is pcm_i16[offsets[r] : offsets[r+1]], and samples outside
+ * [offsets[0], offsets[n_rec]) belong to no recording and are never read.  Recording r has
+ *   W_r = len_r < window ? 0 : 1 + (len_r - window) / stride
+ * windows (0 for a short or empty one) and owns rows [window0[r], window0[r+1]) of
+ * out [sum W_r][1 + window/hop][n_dct] (PCEN: n_mels), window0 the prefix sum of W_r.  Those
+ * rows equal, bit for bit, what honk_mfcc_windows_i16 (honk_pcen_windows_i16) writes for that
+ * recording alone with first_window = 0, n_windows = W_r: reflect padding about each window's
+ * own bounds, each interior frame of a recording computed once for all of that recording's
+ * windows, nothing read across a recording boundary, the same fixed-order per-frame arithmetic.
+ *
+ * One route (shared overlapping / shared gapped / unshared: a function of the geometry alone)
+ * for the whole batch.  Segment tiles are laid out per recording, as the single-recording call
+ * lays out that recording's, in recording order; edge tiles run over the batch's global window
+ * index, so one edge tile holds windows of several recordings and a tick of many one-window
+ * streams fills its edge tiles:
+ *   tiles = sum_r seg_tiles_r + ceil(2 * sum W_r / groups_per_tile)     (unshared: the sum only)
+ * A workgroup (in an edge tile: each group) finds its recording by a binary search over a
+ * per-recording table in device memory: n_rec + 1 rows of six int64 (first segment tile, first
+ * window, first shared-frame row, offsets[r], W_r, shared frames; the last row holds the totals).
+ *
+ * honk_*_segments_plan (host-only) validate offsets and fill the counts (sums over the
+ * recordings of the single-recording plans), window0 [n_rec + 1] (may be NULL) and the table
+ * (host memory of table_capacity bytes; NULL: sizes only; shorter than table_bytes:
+ * HONK_ERR_WORKSPACE).  The caller copies the table to the device (table_dev).  The _i16 calls
+ * take the host offsets again (the grid size; re-validated against total_samples) and only
+ * enqueue on `stream`: no synchronisation, no allocation, no copy; capturable while pcm_i16,
+ * table_dev, out and workspace keep their addresses and the offsets stay the same.  PCEN: on
+ * the overlapping route the workspace holds [sum G_r][n_mels] shared E rows, then
+ * [sum W_r][head + tail][n_mels] edge rows; stage 2 is one workgroup per global window.
+ * n_rec == 0 or sum W_r == 0: HONK_OK, nothing enqueued (shape and parameters are checked first).
+ * Status as the single-recording calls: HONK_ERR_ARG (a null pointer, a negative count, offsets
+ * that decrease, are negative or run past total_samples, stride < 1, window <= n_fft/2, the PCEN
+ * parameter refusals); HONK_ERR_UNSUPPORTED (n_fft or hop not a multiple of 16, more than 128
+ * mel bands, the LDS plans, more than 2^31 - 1 tiles); HONK_ERR_WORKSPACE (a short workspace or
+ * table).  Memory contract: the workspace's contents on entry are ignored and only
+ * [0, workspace_bytes) of the plan is touched; out is fully written and nothing outside it;
+ * pcm_i16 and table_dev are never modified.
+ */
+typedef struct honk_mfcc_segments_plan_t {
+  int64_t windows;          /* sum W_r: rows of out                                        */
+  int64_t shared_frames, edge_frames, frames_computed;   /* sums over the recordings       */
+  int64_t tiles;            /* workgroups of the frame-tile kernel (formula above)         */
+  int64_t workspace_bytes;  /* device workspace                                            */
+  int64_t table_bytes;      /* the per-recording table: filled on the host, read on device */
+  int32_t shared, frames;
+} honk_mfcc_segments_plan_t;
+int honk_mfcc_segments_plan(const int64_t* offsets, int64_t n_rec, int32_t window, int32_t stride,
+                            int32_t n_fft, int32_t hop,
+                            int64_t* window0 /* host [n_rec+1], may be NULL */,
+                            void* table /* host, may be NULL: sizes only */, size_t table_capacity,
+                            honk_mfcc_segments_plan_t* plan);
+int honk_mfcc_segments_i16(const int16_t* pcm_i16, int64_t total_samples, const int64_t* offsets, int64_t n_rec,
+                           const void* table_dev, size_t table_bytes, int32_t window, int32_t stride,
+                           const float* window_tbl, int32_t n_fft, int32_t hop, const float* mel_weights,
+                           int32_t n_mels, const float* dct, int32_t n_dct, float* out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int honk_pcen_segments_plan(const int64_t* offsets, int64_t n_rec, int32_t window, int32_t stride,
+                            int32_t n_fft, int32_t hop, int32_t n_mels,
+                            int64_t* window0 /* host [n_rec+1], may be NULL */,
+                            void* table /* host, may be NULL: sizes only */, size_t table_capacity,
+                            honk_mfcc_segments_plan_t* plan);
+int honk_pcen_segments_i16(const int16_t* pcm_i16, int64_t total_samples, const int64_t* offsets, int64_t n_rec,
+                           const void* table_dev, size_t table_bytes, int32_t window, int32_t stride,
+                           const float* window_tbl, int32_t n_fft, int32_t hop, const float* mel_weights,
+                           int32_t n_mels, const honk_pcen_params_t* params /* NULL = defaults */,
+                           float* out /* [sum W_r][1 + window/hop][n_mels] */,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training (data-parallel train(), utils/train.py:99-135) -------------------- */
 /*
