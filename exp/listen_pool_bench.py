@@ -1,18 +1,22 @@
 """Many live streams at once: a StreamPool tick (one label_streams call: one upload, one ragged-batch
 front-end call, one forward, one download) against S StreamListener.feed calls (one label_stream
-round trip per stream -- the code path the pool leaves unchanged) (one GPU, cuda:0).
+round trip per stream -- the code path the pool leaves unchanged), and against a
+StreamPool(device_state=True) tick (tails and finished rows resident on the device: only the new bytes
+uploaded, only the new frames computed) (one GPU, cuda:0).
 
     python exp/listen_pool_bench.py [--streams 1 64 1024] [--ticks 100 500] [--fronts mfcc pcen]
                                     [--reps 7] [--out profiles/listen_pool_bench.json]
 
 Per front end, tick length (ms of audio per stream per tick, the stride being the tick) and number of
 streams S, back to back in one process: every stream is primed with one second, so each further tick
-completes exactly one window per stream.  After a warm-up tick of both routes, --reps timed ticks each,
-alternating, the device synchronised around every timed region:
-  (a) end to end (host clock): StreamPool.feed({k: chunk_k}) against [listener_k.feed(chunk_k)]; both
-      sides see the same chunks;
-  (b) the front end's device time alone (events; the S one-second recordings already on the device):
-      one compute_*_segments against S compute_*_windows calls.
+completes exactly one window per stream.  After a warm-up tick of every route, --reps timed ticks each,
+alternating tick by tick, the device synchronised around every timed region:
+  (a) end to end (host clock): StreamPool.feed({k: chunk_k}) against [listener_k.feed(chunk_k)] and
+      against StreamPool(device_state=True).feed({k: chunk_k}); all sides see the same chunks;
+  (b) the front end's device time alone (events; the samples already on the device): one
+      compute_*_segments on the S one-second recordings against S compute_*_windows calls, and against
+      one StreamBank.tick on the S new chunks of a primed bank; with the bank tick's samples_in,
+      frames_computed and frames_reused.
 Next to them the frame-tile workgroups: the batch plan's `tiles` and the sum of the S single-recording
 calls' (each rounds its edge tile up on its own).
 Prints one JSON line (median, min, max per figure, ms); --out also writes it to a file."""
@@ -107,6 +111,10 @@ def main():
                 r["tiles"] = {"pool": int(plan.tiles), "per_stream_sum": S * int(one.tiles)}
                 # (a) end to end
                 pool = hs.StreamPool(svc, ms)
+                bank_pool = hs.StreamPool(svc, ms, device_state=True)
+                assert bank_pool.bank is not None
+                first = bank_pool.feed({k: w[:2 * WIN] for k, w in enumerate(wavs)})
+                assert all(len(first[k]) == 1 for k in range(S))
                 listeners = [hs.StreamListener(svc, ms) for _ in range(S)]
                 first = pool.feed({k: w[:2 * WIN] for k, w in enumerate(wavs)})
                 assert all(len(first[k]) == 1 for k in range(S))
@@ -127,22 +135,37 @@ def main():
                     for sl, b in zip(listeners, c):
                         assert len(sl.feed(b)) == 1
 
-                t = {"pool": [], "per_stream": []}
+                def run_bank(c):
+                    got = bank_pool.feed(dict(enumerate(c)))
+                    assert all(len(got[k]) == 1 for k in range(S))
+
+                t = {"pool": [], "per_stream": [], "bank": []}
+                fed = []
                 for rep in range(a.reps + 1):
-                    c = chunks()   # (the pool's streams and the listeners are at the same position: the same chunks)
-                    for name, fn_ in (("pool", run_pool), ("per_stream", run_loop)):
+                    c = chunks()   # (every route's streams are at the same position: the same chunks)
+                    fed.append(c)
+                    for name, fn_ in (("pool", run_pool), ("per_stream", run_loop), ("bank", run_bank)):
                         dt = host_timed(lambda: fn_(c))
                         if rep:
                             t[name].append(dt)
                 r["end_to_end_ms"] = {k: stat(v) for k, v in t.items()}
                 r["end_to_end_ratio"] = round(statistics.median(t["per_stream"]) / statistics.median(t["pool"]), 3)
+                r["end_to_end_pool_over_bank"] = round(statistics.median(t["pool"]) / statistics.median(t["bank"]), 3)
                 r["ticks_per_second_pool"] = round(1.0 / statistics.median(t["pool"]), 1)
+                r["ticks_per_second_bank"] = round(1.0 / statistics.median(t["bank"]), 1)
                 # (b) the front end's device time alone, S one-second recordings on the device
                 pcm = torch.from_numpy(np.concatenate([np.frombuffer(w, np.int16, WIN) for w in wavs])).to(dev)
                 recs = [pcm[k * WIN:(k + 1) * WIN] for k in range(S)]
                 x, w0 = segments(pcm, off, step)
                 assert x.shape[0] == S and torch.equal(x[S - 1], windows(recs[S - 1], step)[0])
-                t = {"pool": [], "per_stream": []}
+                # a bank primed with the same second of every stream; each timed tick feeds the next chunks
+                bank = pre.stream_bank(step, WIN, "PCEN" if front == "pcen" else "MFCCs", dev, slots=S)
+                ids = [bank.open() for _ in range(S)]
+                xb, _ = bank.tick(ids, pcm, off)
+                assert torch.equal(xb, x)
+                new = [torch.from_numpy(np.concatenate([np.frombuffer(b, np.int16) for b in c])).to(dev) for c in fed]
+                noff = np.arange(S + 1, dtype=np.int64) * step
+                t = {"pool": [], "per_stream": [], "bank": []}
                 fns = {"pool": lambda: segments(pcm, off, step),
                        "per_stream": lambda: [windows(rec, step) for rec in recs]}
                 for rep in range(a.reps + 1):
@@ -150,10 +173,19 @@ def main():
                         dt = device_timed(fn_)
                         if rep:
                             t[name].append(dt)
+                    before = dict(bank.stats)
+                    dt = device_timed(lambda: bank.tick(ids, new[rep], noff))
+                    if rep:
+                        t["bank"].append(dt)
+                r["bank_tick"] = {k: bank.stats[k] - before[k]
+                                  for k in ("samples_in", "windows", "frames_computed", "frames_reused")}
+                r["segments_tick"] = {"samples_in": S * WIN, "windows": S, "frames_computed": int(plan.frames_computed)}
                 r["front_end_device_ms"] = {k: stat(v) for k, v in t.items()}
+                r["front_end_device_pool_over_bank"] = round(
+                    statistics.median(t["pool"]) / statistics.median(t["bank"]), 3)
                 r["front_end_device_ratio"] = round(statistics.median(t["per_stream"]) / statistics.median(t["pool"]), 3)
                 res.setdefault(str(ms), {})[str(S)] = r
-                del pcm, recs, x
+                del pcm, recs, x, xb, new, bank
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:

@@ -53,6 +53,28 @@ class MfccSegmentsPlan(ctypes.Structure):
         "table_bytes")] + [("shared", ctypes.c_int32), ("frames", ctypes.c_int32)]
 
 
+class BankSlot(ctypes.Structure):
+    """honk_bank_slot_t: the host's bookkeeping of one stream-bank slot."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("tail", "cached", "skip", "parity")]
+
+
+class StreamBankPlan(ctypes.Structure):
+    """honk_stream_bank_plan_t."""
+    _fields_ = [("slot_bytes", ctypes.c_int64)] + [(n, ctypes.c_int32) for n in (
+        "tail_capacity", "cache_rows", "route", "frames", "row_floats", "flo", "fhi", "q")]
+
+
+class BankTickPlan(ctypes.Structure):
+    """honk_bank_tick_plan_t."""
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "windows", "frames_computed", "frames_reused", "edge_frames", "tiles", "workspace_bytes", "table_bytes",
+        "samples_in")]
+
+
+BANK_SLOT_DTYPE = [("tail", "<i4"), ("cached", "<i4"), ("skip", "<i4"), ("parity", "<i4")]  # numpy view of BankSlot
+BANK_ROUTES = {0: "unshared", 1: "overlap", 2: "gapped"}
+
+
 class FrontPlan(ctypes.Structure):
     """honk_front_plan_t."""
     _fields_ = [(n, ctypes.c_int32) for n in ("route", "frames", "n_bins", "launches")] + [
@@ -216,6 +238,25 @@ _PROTOS = {
                                               c_f32p, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32,
                                               ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
                                               ctypes.c_void_p]),
+    "honk_stream_bank_plan": (ctypes.c_int, [ctypes.c_int32] * 5 + [ctypes.c_void_p]),
+    "honk_mfcc_bank_tick_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int64] + [ctypes.c_int32] * 5
+                                 + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "honk_pcen_bank_tick_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int64] + [ctypes.c_int32] * 5
+                                 + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "honk_mfcc_bank_tick_i16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32,
+                                               c_f32p, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32,
+                                               c_f32p, ctypes.c_int32, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.c_void_p]),
+    "honk_pcen_bank_tick_i16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32,
+                                               c_f32p, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32,
+                                               ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.c_void_p]),
     "honk_spatial_mean_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_spatial_mean_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_cross_entropy_f32": (ctypes.c_int, [c_f32p, ctypes.c_void_p, c_f32p, ctypes.c_int64, ctypes.c_int32,

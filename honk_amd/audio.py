@@ -430,6 +430,14 @@ class AudioPreprocessor(object):
         recording r's rows are ``compute_pcen_windows`` of that recording alone, bit for bit."""
         return self._compute_segments("pcen", pcm, offsets, stride, window)
 
+    # -- streams fed tick after tick, their tails and finished rows kept on the device ---------------
+    def stream_bank(self, stride, window=16000, front="MFCCs", device=None, slots=64):
+        """A ``StreamBank`` of this front end: ``compute_mfccs_segments`` (``front="PCEN"``:
+        ``compute_pcen_segments``) for streams that arrive in chunks, fed only their new samples.
+        device None: the current ROCm device where there is one, else the CPU.  A shape the plan refuses
+        raises ValueError."""
+        return StreamBank(self, stride, window, front, device, slots)
+
     def _windows_workspace(self, device, nbytes):
         import torch
         key = str(device)
@@ -438,3 +446,175 @@ class AudioPreprocessor(object):
             cache[key] = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
             self._dev_ws = cache
         return cache[key]
+
+
+BANK_TABLE_ROW = 96  # bytes of a row of a bank tick's table (csrc/mfcc_stream.hip BankRec)
+
+
+class StreamBank(object):
+    """Streams that arrive in chunks, fed only their new samples (honk_*_bank_tick_i16,
+    csrc/mfcc_stream.hip; include/honk_hip.h has the contract).  Each open stream owns a slot of device
+    memory holding its unconsumed samples and, where windows overlap on whole hops, the finished rows its
+    next window reuses.
+
+    ``slot = open()``; ``tick(slot_ids, pcm, offsets) -> (x, window0)`` with ``pcm`` the new samples of the
+    fed slots concatenated (1-D int16; a CPU tensor is uploaded once) and stream r's chunk
+    ``pcm[offsets[r]:offsets[r + 1]]``: rows ``x[window0[r]:window0[r + 1]]`` are the windows the chunk
+    completes -- over any chunking, bit for bit the rows of ``compute_mfccs_windows``
+    (``compute_pcen_windows``) on the whole stream.  ``close(slot)`` frees the slot for reuse.  The bank
+    doubles when ``open`` runs out of slots.  ``stats``: cumulative ticks, samples_in (samples handed to
+    the device), windows, frames_computed, frames_reused.
+
+    On a CPU device the tails are numpy arrays and a tick is ``compute_*_windows`` per stream: the same
+    bookkeeping, results and counters (the counters are the plan's arithmetic)."""
+
+    def __init__(self, ap, stride, window=16000, front="MFCCs", device=None, slots=64):
+        import torch
+        from . import _native
+        if front not in ("MFCCs", "PCEN"):
+            raise ValueError(f"stream_bank: front {front!r}")
+        self.ap, self.stride, self.window, self.front = ap, int(stride), int(window), front
+        if self.stride < 1 or self.window < 1 or int(slots) < 1:
+            raise ValueError("stream_bank: stride >= 1, window >= 1, slots >= 1")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        self.pcen = front == "PCEN"
+        self.cols = (ap._mel if self.pcen else ap.dct_filters).shape[0]
+        self.frames = ap.n_frames(self.window)
+        self.plan = _native.StreamBankPlan()
+        lib = _native.load()
+        rc = lib.honk_stream_bank_plan(self.window, self.stride, ap.n_fft, ap.hop_length, self.cols,
+                                       ctypes.addressof(self.plan))
+        if rc == 0:  # the front end's own refusals (PCEN: the mel bands, stage 2's tile)
+            rc = self._plan(np.zeros(0, np.int64), np.zeros(1, np.int64), np.zeros(1, _native.BANK_SLOT_DTYPE))[0]
+        if rc != 0:
+            raise ValueError("stream_bank: " + lib.honk_last_error().decode(errors="replace"))
+        self.route = _native.BANK_ROUTES[self.plan.route]
+        self.stats = dict(ticks=0, samples_in=0, windows=0, frames_computed=0, frames_reused=0)
+        self._slots = np.zeros(int(slots), _native.BANK_SLOT_DTYPE)
+        self._open = np.zeros(int(slots), bool)
+        self._tails = {}  # CPU device: slot -> int16 array
+        self._state = None
+        if self.device.type != "cpu":
+            self._state = torch.empty(int(slots) * int(self.plan.slot_bytes), dtype=torch.uint8, device=self.device)
+
+    @property
+    def slots(self):
+        return len(self._slots)
+
+    def open(self):
+        import torch
+        free = np.flatnonzero(~self._open)
+        if free.size == 0:  # double, existing state preserved
+            n = len(self._slots)
+            self._slots = np.concatenate([self._slots, np.zeros(n, self._slots.dtype)])
+            self._open = np.concatenate([self._open, np.zeros(n, bool)])
+            if self._state is not None:
+                grown = torch.empty(2 * self._state.numel(), dtype=torch.uint8, device=self.device)
+                grown[:self._state.numel()].copy_(self._state)
+                self._state = grown
+            free = np.flatnonzero(~self._open)
+        slot = int(free[0])
+        self._open[slot] = True
+        self._slots[slot] = (0, 0, 0, 0)
+        self._tails.pop(slot, None)
+        return slot
+
+    def close(self, slot):
+        slot = int(slot)
+        if not (0 <= slot < len(self._slots) and self._open[slot]):
+            raise ValueError(f"stream_bank: slot {slot} is not open")
+        self._open[slot] = False
+        self._slots[slot] = (0, 0, 0, 0)
+        self._tails.pop(slot, None)
+
+    def _plan(self, ids, off, slots):
+        """honk_*_bank_tick_plan -> (status, BankTickPlan, window0, next states, table bytes); host-only."""
+        from . import _native
+        n = len(ids)
+        plan = _native.BankTickPlan()
+        window0 = np.zeros(n + 1, np.int64)
+        nxt = np.zeros(n, _native.BANK_SLOT_DTYPE)
+        table = np.zeros(BANK_TABLE_ROW * (n + 1), np.uint8)
+        fn = _native.load().honk_pcen_bank_tick_plan if self.pcen else _native.load().honk_mfcc_bank_tick_plan
+        rc = fn(slots.ctypes.data, len(slots), ids.ctypes.data, off.ctypes.data, n, self.window, self.stride,
+                self.ap.n_fft, self.ap.hop_length, self.cols, window0.ctypes.data, nxt.ctypes.data, table.ctypes.data,
+                table.nbytes, ctypes.addressof(plan))
+        return rc, plan, window0, nxt, table
+
+    def tick(self, slot_ids, pcm, offsets):
+        import torch
+        from . import _native
+        if pcm.dim() != 1 or pcm.dtype != torch.int16:
+            raise ValueError("stream_bank: pcm must be a 1-D int16 tensor")
+        ids = np.ascontiguousarray(np.asarray(slot_ids, dtype=np.int64).reshape(-1))
+        off = AudioPreprocessor._segment_offsets("stream_bank", offsets, pcm.shape[0])
+        n = len(ids)
+        if off.size != n + 1:
+            raise ValueError("stream_bank: offsets must have one entry more than slot_ids")
+        if ((ids < 0) | (ids >= len(self._slots))).any() or not self._open[ids].all() or len(set(ids.tolist())) != n:
+            raise ValueError("stream_bank: slot_ids must be distinct open slots")
+        # stride > window: the samples before a stream's next window are dropped here, before any upload
+        slots, skip = self._slots, self._slots["skip"][ids]
+        if n and (skip > 0).any():
+            lens = np.diff(off)
+            drop = np.minimum(skip, lens)
+            slots = self._slots.copy()   # (committed with the tick)
+            slots["skip"][ids] = skip - drop
+            parts = [pcm[off[r] + drop[r]:off[r + 1]] for r in range(n)]
+            pcm = torch.cat(parts) if parts else pcm[:0]
+            off = np.concatenate([[0], np.cumsum(lens - drop)]).astype(np.int64)
+        rc, plan, window0, nxt, table = self._plan(ids, off, slots)
+        if rc != 0:
+            raise ValueError("stream_bank: " + _native.load().honk_last_error().decode(errors="replace"))
+        if self._state is None:
+            x = self._tick_cpu(ids, pcm, off, plan, nxt)
+        else:
+            x = self._tick_device(ids, pcm, off, plan, table, slots)
+        self._slots = slots
+        self._slots[ids] = nxt
+        st = self.stats
+        st["ticks"] += 1
+        for k in ("samples_in", "windows", "frames_computed", "frames_reused"):
+            st[k] += int(getattr(plan, k))
+        return x, window0
+
+    def _tick_cpu(self, ids, pcm, off, plan, nxt):
+        import torch
+        windows = self.ap.compute_pcen_windows if self.pcen else self.ap.compute_mfccs_windows
+        x = pcm.cpu().numpy()
+        parts = []
+        for r, slot in enumerate(ids.tolist()):
+            buf = np.concatenate([self._tails.get(slot, x[:0]), x[off[r]:off[r + 1]]])
+            rows = windows(torch.from_numpy(buf), self.stride, self.window)
+            parts.append(rows)
+            self._tails[slot] = buf[len(buf) - int(nxt["tail"][r]):].copy()
+        out = torch.cat(parts) if parts else torch.empty(0, self.frames, self.cols, dtype=torch.float32)
+        assert out.shape[0] == plan.windows
+        return out
+
+    def _tick_device(self, ids, pcm, off, plan, table, slots):
+        import torch
+        from . import _native
+        ap, dev = self.ap, self.device
+        out = torch.empty(int(plan.windows), self.frames, self.cols, dtype=torch.float32, device=dev)
+        if plan.samples_in == 0:
+            return out
+        chunks = pcm.to(dev).contiguous()
+        win, mel, dct = ap._device_tables(dev)
+        ws = ap._windows_workspace(dev, plan.workspace_bytes)
+        table_dev = torch.from_numpy(table).to(dev)
+        head = (chunks.data_ptr(), slots.ctypes.data, len(slots), ids.ctypes.data, off.ctypes.data, len(ids),
+                table_dev.data_ptr(), table.nbytes, self._state.data_ptr(), self._state.numel(), self.window,
+                self.stride, win.data_ptr(), ap.n_fft, ap.hop_length, mel.data_ptr(), mel.shape[0])
+        tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_handle(dev))
+        with torch.cuda.device(dev):
+            if self.pcen:
+                p = ap.pcen_params
+                params = _native.PcenParams(p["eps"], p["s"], p["alpha"], p["delta"], p["r"], int(p["power"]))
+                rc = _native.load().honk_pcen_bank_tick_i16(*head, ctypes.addressof(params), *tail)
+            else:
+                rc = _native.load().honk_mfcc_bank_tick_i16(*head, dct.data_ptr(), self.cols, *tail)
+        _native.check(rc, "honk_pcen_bank_tick_i16" if self.pcen else "honk_mfcc_bank_tick_i16")
+        return out

@@ -44,6 +44,15 @@
 // recording's rows are, bit for bit, the single-recording call's -- the per-frame arithmetic is the
 // same code.  PCEN: [sum G_r][n_mels] shared rows, then [sum W_r][head + tail][n_mels] edge rows in
 // the workspace; stage 2 one workgroup per global window.
+//
+// Streams fed tick after tick (honk_mfcc_bank_tick_i16 / honk_pcen_bank_tick_i16): the same kernels
+// (SRC_BANK) over "tail | chunk" of each fed stream, the tail and the finished rows the stream's next
+// window reuses resident in a slot of caller memory between ticks; a row finished in one tick is, bit for
+// bit, the row a later tick would compute, so a stream's rows over any chunking are the single-recording
+// call's on the whole stream.  The layout and the hazard argument stand before bank_assemble_kernel.
+#include <algorithm>
+#include <vector>
+
 #include "common.h"
 #include "pcen_scan.h"
 
@@ -63,6 +72,10 @@ enum { MODE_UNSHARED = 0, MODE_OVERLAP = 1, MODE_GAPPED = 2 };
 // the epilogue of the frame-tile kernel: MFCC frames fanned out to their windows, or the mel
 // energies of |X| (power 1) / |X|^2 (power 2), each frame's row stored once
 enum { EPI_MFCC = 0, EPI_PCEN1 = 1, EPI_PCEN2 = 2 };
+// where the frame-tile kernel's recordings lie: one recording (Args), a batch located by a table of Rec
+// (honk_*_segments_i16), or the fed streams of a stream-bank tick located by a table of BankRec
+// (honk_*_bank_tick_i16: "tail | chunk" assembled in the workspace, finished rows also kept in the slots)
+enum { SRC_ONE = 0, SRC_SEG = 1, SRC_BANK = 2 };
 
 // one row of the per-recording table of the batched calls (honk_*_segments_i16): filled on the host by
 // the plan call, read on the device.  Row n_rec is a sentinel holding the totals, so the last r with
@@ -74,6 +87,32 @@ struct Rec {
   int64_t sample0;  // offsets[r]
   int64_t n;        // windows
   int64_t G;        // MODE_OVERLAP: shared frames
+};
+
+// one row of a stream-bank tick's table (honk_*_bank_tick_i16): the first six fields as Rec's, for the
+// stream's "recording" of this tick -- tail | chunk, assembled in the workspace at sample0.  On the
+// overlapping route the stream's virtual window starts with `cached` finished rows kept from earlier ticks:
+// G counts only the frames jl >= flo + cached computed now, srow0 their first row
+struct BankRec {
+  int64_t tile0, window0, srow0, sample0, n, G;
+  int64_t slot;       // the stream's slot of state_dev
+  int64_t chunk0;     // chunk_offsets[r]
+  int64_t chunk_len;  // new samples
+  int64_t consumed;   // samples of tail | chunk the tick's windows use up: the new tail starts there
+  int32_t tail;       // samples in the slot before the tick
+  int32_t cached;     // rows of the slot's cache the tick reuses
+  int32_t half;       // the cache half that holds them; the tick writes the other one
+  int32_t new_tail;   // samples in the slot after the tick
+};
+
+// the slots of a stream bank: [tail_bytes of int16][2 halves of half_floats floats] each
+struct BankGeo {
+  char* state;
+  int64_t slot_bytes, tail_bytes, half_floats;
+  __host__ __device__ int16_t* tail(int64_t slot) const { return (int16_t*)(state + slot * slot_bytes); }
+  __host__ __device__ float* cache(int64_t slot, int half) const {
+    return (float*)(state + slot * slot_bytes + tail_bytes) + half * half_floats;
+  }
 };
 
 struct Args {
@@ -96,6 +135,9 @@ struct Args {
   // a batch of recordings (SEG kernels): n, G and seg_tiles are the batch's totals, first_sample is unused
   const Rec* table;  // [n_rec + 1]
   int64_t n_rec;
+  // a stream-bank tick (SRC_BANK kernels): as a batch, the fed streams for recordings
+  const BankRec* btable = nullptr;  // [n_rec + 1]
+  BankGeo bank = {};
 };
 
 struct Group {
@@ -106,6 +148,10 @@ struct Group {
   int64_t n;     // windows of the group's recording
   int64_t srow;  // MODE_OVERLAP: the recording's first shared-frame row
   int nf;        // frames (0: an empty group)
+  // SRC_BANK, MODE_OVERLAP segments: a finished frame jl >= jc of the virtual window is also row jl - jc
+  // of the slot's new cache (null: the bank keeps no rows)
+  float* cnew;
+  int64_t jc;
 };
 
 __device__ __forceinline__ int64_t reflect(int64_t i, int64_t n) {
@@ -116,8 +162,8 @@ __device__ __forceinline__ int64_t reflect(int64_t i, int64_t n) {
 }
 
 // the last row r < n_rec of the table with tile0 (BY_TILE) / window0 <= v: log2(n_rec) steps
-template <bool BY_TILE>
-__device__ __forceinline__ const Rec& rec_of(const Rec* table, int64_t n_rec, int64_t v) {
+template <bool BY_TILE, class R>
+__device__ __forceinline__ const R& rec_of(const R* table, int64_t n_rec, int64_t v) {
   int64_t lo = 0, hi = n_rec;
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;
@@ -129,23 +175,36 @@ __device__ __forceinline__ const Rec& rec_of(const Rec* table, int64_t n_rec, in
   return table[lo > 0 ? lo - 1 : 0];
 }
 
-template <bool SEG>
+template <int SRC>
 __device__ __forceinline__ Group group_of(const Args& a, int64_t t, int gi) {
   Group g;
+  g.cnew = nullptr;
+  g.jc = 0;
   if (t < a.seg_tiles) {
     int64_t first = a.first_sample, n = a.n, G = a.G, w0 = 0, tl = t;
+    int cached = 0;
     g.srow = 0;
-    if constexpr (SEG) {
+    if constexpr (SRC == SRC_SEG) {
       const Rec& r = rec_of<true>(a.table, a.n_rec, t);
       first = r.sample0; n = r.n; G = r.G; w0 = r.window0; tl = t - r.tile0;
       g.srow = r.srow0;
+    }
+    if constexpr (SRC == SRC_BANK) {
+      const BankRec& r = rec_of<true>(a.btable, a.n_rec, t);
+      first = r.sample0; n = r.n; G = r.G; w0 = r.window0; tl = t - r.tile0;
+      cached = r.cached;
+      g.srow = r.srow0 - cached;  // (so that row srow + jl - flo is the computed frame jl's)
+      if (a.mode == MODE_OVERLAP && a.bank.half_floats > 0) {
+        g.cnew = a.bank.cache(r.slot, 1 - r.half);
+        g.jc = n * a.q + a.flo;
+      }
     }
     g.n = n;
     if (a.mode == MODE_OVERLAP) {
       g.base = first;
       g.L = (n - 1) * a.stride + a.win_len;
       g.wl = w0;
-      g.f0 = a.flo + tl * FT;
+      g.f0 = a.flo + cached + tl * FT;
       g.nf = (int)min((int64_t)FT, G - tl * FT);
     } else {
       const int fa = a.mode == MODE_GAPPED ? a.flo : 0;
@@ -164,10 +223,17 @@ __device__ __forceinline__ Group group_of(const Args& a, int64_t t, int gi) {
     g.srow = 0;
     const bool live = g.wl < a.n && gi < a.gpt;
     g.base = a.first_sample + g.wl * a.stride;
-    if constexpr (SEG) {
+    if constexpr (SRC == SRC_SEG) {
       g.base = 0;
       if (live) {
         const Rec& r = rec_of<false>(a.table, a.n_rec, g.wl);
+        g.base = r.sample0 + (g.wl - r.window0) * a.stride;
+      }
+    }
+    if constexpr (SRC == SRC_BANK) {
+      g.base = 0;
+      if (live) {
+        const BankRec& r = rec_of<false>(a.btable, a.n_rec, g.wl);
         g.base = r.sample0 + (g.wl - r.window0) * a.stride;
       }
     }
@@ -201,8 +267,11 @@ __global__ __launch_bounds__(64) void mel_range_kernel(const float* melw, int n_
 
 // SEG: a batch of recordings -- every group finds its recording in a.table once (one lane per group,
 // the groups kept in LDS behind the power tile), before staging
-template <int EPI, bool SEG = false>
+// SRC_BANK: the same over the fed streams of a tick, frames jl < flo + cached left to the cache kernel; a
+// finished row the stream's next window reuses is stored to the slot's new cache half as well
+template <int EPI, int SRC = SRC_ONE>
 __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
+  constexpr bool SEG = SRC != SRC_ONE;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int N = a.n_fft, NB = a.n_bins, NM = a.n_mels, ND = a.n_dct, hop = a.hop, pad = N / 2;
   const int PS = NB | 1;            // odd row stride of the power tile
@@ -220,14 +289,14 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
   const int glen = (gs - 1) * hop + N;
   Group* grp = (Group*)(pw + FT * PS);  // [ng] (SEG; 8-byte aligned: every term before it is even)
   if constexpr (SEG) {
-    if (tid < ng) grp[tid] = group_of<true>(a, t, tid);
+    if (tid < ng) grp[tid] = group_of<SRC>(a, t, tid);
     __syncthreads();
   }
   const auto group = [&](int gi) -> Group {
     if constexpr (SEG)
       return grp[gi];
     else
-      return group_of<false>(a, t, gi);
+      return group_of<SRC_ONE>(a, t, gi);
   };
 
   for (int gi = 0; gi < ng; ++gi) {
@@ -317,12 +386,16 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
       lm[f * (NM + 1) + m] = s;
     }
     int64_t* erow = (int64_t*)(lm + FT * (NM + 1));  // [FT] the slot's row of a.out, -1: none (8-byte aligned)
+    float** cdst = (float**)(erow + FT);             // [FT] SRC_BANK: the slot's row of the new cache, or null
     if (tid < FT) {
       const int gi = tid / gs, fi = tid - gi * gs;
       int64_t row = -1;
+      float* keep = nullptr;
       if (gi < ng) {
         const Group gr = group(gi);
         if (fi < gr.nf) {
+          if constexpr (SRC == SRC_BANK)
+            if (!edge && gr.cnew && gr.f0 + fi >= gr.jc) keep = gr.cnew + (gr.f0 + fi - gr.jc) * NM;
           if (a.mode != MODE_OVERLAP)
             row = gr.wl * a.frames + gr.f0 + fi;
           else if (!edge)
@@ -332,11 +405,14 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
         }
       }
       erow[tid] = row;
+      if constexpr (SRC == SRC_BANK) cdst[tid] = keep;
     }
     __syncthreads();
     for (int e = tid; e < FT * NM; e += blockDim.x) {
       const int s = e / NM, m = e - s * NM;
       if (erow[s] >= 0) a.out[erow[s] * NM + m] = lm[s * (NM + 1) + m];
+      if constexpr (SRC == SRC_BANK)
+        if (cdst[s]) cdst[s][m] = lm[s * (NM + 1) + m];
     }
     return;
   }
@@ -360,16 +436,20 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
   // where each slot goes: output rows row0 + d (frames - q), d < count -- window wl0 + d, frame f0 - d q
   int64_t* srow = (int64_t*)(ot + FT * (ND + 1));  // [FT] (8-byte aligned: FT is even)
   int* scnt = (int*)(srow + FT);                   // [FT]
+  float** cdst = (float**)(scnt + FT);             // [FT] SRC_BANK: the slot's row of the new cache, or null
   const bool fan = !edge && a.mode == MODE_OVERLAP;
   if (tid < FT) {
     const int gi = tid / gs, fi = tid - gi * gs;
     int64_t row = 0;
     int cnt = 0;
+    float* keep = nullptr;
     if (gi < ng) {
       const Group gr = group(gi);
       if (fi < gr.nf) {
         if (fan) {
           const int64_t jl = gr.f0 + fi;  // frame of the virtual window: frame jl - w q of window w
+          if constexpr (SRC == SRC_BANK)
+            if (gr.cnew && jl >= gr.jc) keep = gr.cnew + (jl - gr.jc) * ND;
           const int64_t wlo = jl > a.fhi ? (jl - a.fhi + a.q - 1) / a.q : 0;
           const int64_t whi = min(gr.n - 1, (jl - a.flo) / a.q);
           row = (gr.wl + wlo) * a.frames + (jl - wlo * a.q);
@@ -382,6 +462,7 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
     }
     srow[tid] = row;
     scnt[tid] = cnt;
+    if constexpr (SRC == SRC_BANK) cdst[tid] = keep;
   }
   __syncthreads();
   const int cmax = fan ? (a.fhi - a.flo) / a.q + 1 : 1;
@@ -391,6 +472,12 @@ __global__ __launch_bounds__(64 * WAVES) void mfcc_windows_kernel(Args a) {
     const int s = e / per, r = e - s * per;
     const int d = r / ND, i = r - d * ND;
     if (d < scnt[s]) a.out[(srow[s] + d * rstep) * ND + i] = ot[s * (ND + 1) + i];
+  }
+  if constexpr (SRC == SRC_BANK) {
+    for (int e = tid; e < FT * ND; e += blockDim.x) {
+      const int s = e / ND, i = e - s * ND;
+      if (cdst[s]) cdst[s][i] = ot[s * (ND + 1) + i];
+    }
   }
 }
 
@@ -404,6 +491,10 @@ struct ScanArgs {
   int frames, n_mels, flo, fhi, q, mode, nseg;
   const Rec* table;  // a batch of recordings: G is the batch's total, w the global window; else null
   int64_t n_rec;
+  // a stream-bank tick: G the tick's computed shared rows; an interior frame jl < flo + cached of a stream's
+  // virtual window comes from the slot's old cache half, the others from e
+  const BankRec* btable = nullptr;
+  BankGeo bank = {};
 };
 
 // one workgroup per window: E tile -> LDS, smoother + compression there, the window's rows out
@@ -420,10 +511,20 @@ __global__ __launch_bounds__(SCAN_THREADS) void pcen_windows_scan_kernel(ScanArg
       srow = r.srow0 + (w - r.window0) * s.q - s.flo;
     }
     const int64_t erow = s.G + w * ne;
+    const float* old = nullptr;  // the stream's cached rows: frames [wq + flo, wq + flo + nold) of this window
+    int64_t nold = 0;
+    if (s.btable) {
+      const BankRec& r = rec_of<false>(s.btable, s.n_rec, w);
+      const int64_t wq = (w - r.window0) * s.q;
+      srow = r.srow0 - r.cached + wq - s.flo;
+      old = s.bank.cache(r.slot, r.half) + (wq - s.flo) * NM;
+      nold = r.cached - wq;
+    }
     for (int i = threadIdx.x; i < F * NM; i += blockDim.x) {
       const int f = i / NM, m = i - f * NM;
       const int64_t row = f < s.flo ? erow + f : (f > s.fhi ? erow + s.flo + (f - s.fhi - 1) : srow + f);
-      tile[i] = s.e[row * NM + m];
+      const bool cached = f >= s.flo && f <= s.fhi && f - s.flo < nold;
+      tile[i] = cached ? old[(int64_t)f * NM + m] : s.e[row * NM + m];
     }
   } else {
     for (int i = threadIdx.x; i < F * NM; i += blockDim.x) tile[i] = o[i];
@@ -616,6 +717,321 @@ static int segments_layout(const Plan& geo, const SegPlan& sp, const char* who, 
   return HONK_OK;
 }
 
+// ---- a stream bank: tails and finished rows resident between ticks ---------------------- //
+// A slot of state_dev is [tail: the stream's unconsumed samples][two cache halves of cache_rows rows].  A
+// tick is a chain of launches on one stream; within a launch no location is read by one workgroup and
+// written by another:
+//   bank_assemble_kernel  slot tails, chunks_dev -> "tail | chunk" per fed stream in the workspace
+//   mfcc_windows_kernel   <SRC_BANK> workspace -> out (PCEN: E rows in the workspace), the new cache half
+//   pcen_windows_scan     (PCEN) old cache half, workspace -> out
+//   bank_cache_kernel     old cache half -> out (MFCC), the new cache half
+//   bank_tail_kernel      workspace -> slot tails
+// The old and the new cache of a slot are different halves (the host's parity bit flips when a tick
+// completes a window), and the tail goes through the workspace, so no launch updates anything in place.
+constexpr int BANK_THREADS = 256;
+constexpr int BANK_MAX_Y = 64;  // workgroups along a stream's samples in the two copy kernels
+
+__global__ __launch_bounds__(BANK_THREADS) void bank_assemble_kernel(const BankRec* table, BankGeo bank,
+                                                                     const int16_t* chunks, int16_t* pcm) {
+  const BankRec r = table[blockIdx.x];
+  const int16_t* tail = bank.tail(r.slot);
+  const int64_t len = r.tail + r.chunk_len;
+  for (int64_t i = (int64_t)blockIdx.y * BANK_THREADS + threadIdx.x; i < len; i += (int64_t)gridDim.y * BANK_THREADS)
+    pcm[r.sample0 + i] = i < r.tail ? tail[i] : chunks[r.chunk0 + (i - r.tail)];
+}
+
+__global__ __launch_bounds__(BANK_THREADS) void bank_tail_kernel(const BankRec* table, BankGeo bank,
+                                                                 const int16_t* pcm) {
+  const BankRec r = table[blockIdx.x];
+  int16_t* tail = bank.tail(r.slot);
+  const int16_t* src = pcm + r.sample0 + r.consumed;
+  for (int i = blockIdx.y * BANK_THREADS + threadIdx.x; i < r.new_tail; i += gridDim.y * BANK_THREADS)
+    tail[i] = src[i];
+}
+
+// the cached rows of a fed stream that completes n >= 1 windows, FT rows per workgroup (blockIdx.y): row i
+// is frame jl = flo + i of the stream's virtual window.  MFCC (out != null): the fan-out of the frame-tile
+// kernel for that frame -- frame jl - d q of window d, d <= min(n - 1, i / q); jl <= fhi - q, so d starts at
+// 0.  A row i >= n q is row i - n q of the new cache (the frames the tick computes fill the rest)
+__global__ __launch_bounds__(BANK_THREADS) void bank_cache_kernel(const BankRec* table, BankGeo bank, float* out,
+                                                                  int cols, int frames, int flo, int q) {
+  const BankRec r = table[blockIdx.x];
+  const int row0 = blockIdx.y * FT;
+  if (r.n < 1 || row0 >= r.cached) return;
+  const int rows = min(FT, r.cached - row0);
+  const float* old = bank.cache(r.slot, r.half);
+  float* fresh = bank.cache(r.slot, 1 - r.half);
+  for (int e = threadIdx.x; e < rows * cols; e += blockDim.x) {
+    const int i = row0 + e / cols, c = e % cols;
+    const float v = old[(int64_t)i * cols + c];
+    if (out) {
+      const int64_t dmax = min(r.n - 1, (int64_t)(i / q));
+      for (int64_t d = 0; d <= dmax; ++d) out[((r.window0 + d) * frames + (flo + i - d * q)) * cols + c] = v;
+    }
+    if (i >= r.n * q) fresh[(int64_t)(i - r.n * q) * cols + c] = v;
+  }
+}
+
+struct BankPlan {
+  honk_stream_bank_plan_t p;
+  BankGeo geo;  // (state null)
+};
+
+// host-only: the slot layout of a geometry (geo: make_plan's route on a recording without windows)
+static void make_bank_plan(const Plan& geo, int32_t window, int32_t row_floats, BankPlan* bp) {
+  honk_stream_bank_plan_t& p = bp->p;
+  p = honk_stream_bank_plan_t{};
+  const int nint = geo.fhi - geo.flo + 1;
+  p.tail_capacity = window - 1;
+  p.cache_rows = geo.mode == MODE_OVERLAP ? nint - geo.q : 0;
+  p.route = geo.mode;
+  p.frames = geo.p.frames;
+  p.row_floats = row_floats;
+  p.flo = geo.flo; p.fhi = geo.fhi; p.q = geo.q;
+  bp->geo.state = nullptr;
+  bp->geo.tail_bytes = (2 * (int64_t)p.tail_capacity + 15) / 16 * 16;
+  bp->geo.half_floats = (int64_t)p.cache_rows * row_floats;
+  bp->geo.slot_bytes = (bp->geo.tail_bytes + 2 * bp->geo.half_floats * (int64_t)sizeof(float) + 15) / 16 * 16;
+  p.slot_bytes = bp->geo.slot_bytes;
+}
+
+struct TickPlan {
+  honk_bank_tick_plan_t p;
+  int64_t seg_tiles, shared_rows, pcm_offset, max_len;
+};
+
+// host-only: a tick's counts, window0, the next state of the fed slots and the table.  e_floats as
+// make_segments_plan's.  Nothing is written unless the whole tick is accepted
+static int make_tick_plan(const Plan& geo, const BankPlan& bank, const char* who, const honk_bank_slot_t* slots,
+                          int64_t n_slots, const int64_t* slot_ids, const int64_t* offsets, int64_t n_fed,
+                          int32_t window, int32_t stride, int64_t e_floats, int64_t* window0, honk_bank_slot_t* next,
+                          BankRec* table, size_t table_capacity, TickPlan* tp) {
+  if (n_slots < 0 || n_fed < 0) return fail(HONK_ERR_ARG, "negative count");
+  if (!offsets || (n_fed > 0 && (!slots || !slot_ids))) return fail(HONK_ERR_ARG, "null pointer argument");
+  if (offsets[0] < 0) return fail(HONK_ERR_ARG, "%s bank tick: negative offset", who);
+  for (int64_t r = 0; r < n_fed; ++r)
+    if (offsets[r + 1] < offsets[r])
+      return fail(HONK_ERR_ARG, "%s bank tick: offsets decrease at stream %lld", who, (long long)r);
+  honk_bank_tick_plan_t& p = tp->p;
+  p = honk_bank_tick_plan_t{};
+  p.table_bytes = (n_fed + 1) * (int64_t)sizeof(BankRec);
+  if (table && table_capacity < (size_t)p.table_bytes)
+    return fail(HONK_ERR_WORKSPACE, "%s bank tick table: %zu bytes, %lld needed", who, table_capacity,
+                (long long)p.table_bytes);
+  static thread_local std::vector<uint8_t> fed;  // (host bookkeeping of the plan; nothing on the device)
+  fed.assign((size_t)n_slots, 0);
+  const int rows = bank.p.cache_rows;
+  for (int64_t r = 0; r < n_fed; ++r) {
+    const int64_t id = slot_ids[r];
+    if (id < 0 || id >= n_slots)
+      return fail(HONK_ERR_ARG, "%s bank tick: slot %lld of %lld", who, (long long)id, (long long)n_slots);
+    if (fed[(size_t)id]) return fail(HONK_ERR_ARG, "%s bank tick: slot %lld fed twice", who, (long long)id);
+    fed[(size_t)id] = 1;
+    const honk_bank_slot_t& s = slots[id];
+    if (s.tail < 0 || s.tail > bank.p.tail_capacity || (s.cached != 0 && s.cached != rows) || s.skip < 0 ||
+        (s.skip > 0 && s.tail > 0) || (s.parity != 0 && s.parity != 1))
+      return fail(HONK_ERR_ARG, "%s bank tick: slot %lld holds no valid state", who, (long long)id);
+    if (s.skip > 0 && offsets[r + 1] > offsets[r])
+      return fail(HONK_ERR_ARG, "%s bank tick: slot %lld still skips %d samples (stride > window): the caller "
+                  "drops them before the upload", who, (long long)id, s.skip);
+  }
+  const int nint = geo.fhi - geo.flo + 1;
+  const int nfw = geo.mode == MODE_GAPPED ? nint : geo.p.frames;
+  const int64_t tps = cdiv(nfw, FT);
+  int64_t tiles = 0, windows = 0, srow = 0, pos = 0, max_len = 0;
+  for (int64_t r = 0; r < n_fed; ++r) {
+    const honk_bank_slot_t& s = slots[slot_ids[r]];
+    const int64_t c = offsets[r + 1] - offsets[r], len = s.tail + c;
+    const int64_t n = len < window ? 0 : 1 + (len - window) / stride;
+    const int64_t consumed = n * stride < len ? n * stride : len;
+    const int cached = geo.mode == MODE_OVERLAP ? s.cached : 0;
+    const int64_t G = geo.mode == MODE_OVERLAP && n > 0 ? (n - 1) * geo.q + nint - cached : 0;
+    honk_bank_slot_t nx = s;
+    nx.tail = (int32_t)(len - consumed);
+    if (n > 0) {
+      nx.skip = (int32_t)(n * stride - consumed);
+      nx.cached = rows;
+      if (rows > 0) nx.parity = 1 - s.parity;
+    }
+    if (window0) window0[r] = windows;
+    if (next) next[r] = nx;
+    if (table)
+      table[r] = BankRec{tiles, windows, srow, pos, n, G, slot_ids[r], offsets[r], c, consumed, s.tail, cached,
+                         s.parity, nx.tail};
+    if (geo.mode == MODE_UNSHARED) {
+      p.frames_computed += n * geo.p.frames;
+    } else {
+      const int64_t shared = geo.mode == MODE_OVERLAP ? G : n * nint;
+      srow += shared;
+      p.edge_frames += n * (geo.p.frames - nint);
+      p.frames_computed += shared + n * (geo.p.frames - nint);
+      if (n > 0) p.frames_reused += cached;
+    }
+    tiles += geo.mode == MODE_OVERLAP ? cdiv(G, FT) : n * tps;
+    windows += n;
+    pos += len;
+    if (len > max_len) max_len = len;
+  }
+  if (window0) window0[n_fed] = windows;
+  if (table) table[n_fed] = BankRec{tiles, windows, srow, pos, 0, 0, 0, offsets[n_fed], 0, 0, 0, 0, 0, 0};
+  tp->seg_tiles = tiles;
+  tp->shared_rows = srow;
+  tp->max_len = max_len;
+  if (geo.mode != MODE_UNSHARED && geo.gs > 0) tiles += cdiv(2 * windows, FT / geo.gs);
+  p.windows = windows;
+  p.tiles = tiles;
+  p.samples_in = offsets[n_fed] - offsets[0];
+  tp->pcm_offset = (2 * MAX_MELS * (int64_t)sizeof(int) + p.frames_computed * e_floats * (int64_t)sizeof(float) + 15) /
+                   16 * 16;
+  p.workspace_bytes = tp->pcm_offset + 2 * pos;
+  if (tiles > 0x7fffffff || windows > 0x7fffffff || n_fed > 0x7fffffff)
+    return fail(HONK_ERR_UNSUPPORTED, "%s bank tick: too many frame tiles in one call", who);
+  return HONK_OK;
+}
+
+// host-only: the shape checks of both front ends' bank calls -> the route, the slot layout, stage 2's plan
+static int bank_geometry(bool pcen, int32_t window, int32_t stride, int32_t n_fft, int32_t hop, int32_t row_floats,
+                         Plan* geo, BankPlan* bank, int* nseg, size_t* scan_lds) {
+  if (row_floats < 1) return fail(HONK_ERR_ARG, pcen ? "bad pcen arguments" : "bad mfcc arguments");
+  const int rc = pcen ? make_pcen_plan(0, window, stride, n_fft, hop, row_floats, 0, 0, geo, nseg, scan_lds)
+                      : make_plan(0, window, stride, n_fft, hop, 0, 0, geo);
+  if (rc != HONK_OK) return rc;
+  make_bank_plan(*geo, window, row_floats, bank);
+  return HONK_OK;
+}
+
+static int bank_tick_plan(bool pcen, const honk_bank_slot_t* slots, int64_t n_slots, const int64_t* slot_ids,
+                          const int64_t* offsets, int64_t n_fed, int32_t window, int32_t stride, int32_t n_fft,
+                          int32_t hop, int32_t row_floats, int64_t* window0, honk_bank_slot_t* next, void* table,
+                          size_t table_capacity, honk_bank_tick_plan_t* plan) {
+  if (!plan) return fail(HONK_ERR_ARG, "null pointer argument");
+  Plan geo;
+  BankPlan bank;
+  int nseg;
+  size_t scan_lds;
+  const int rc = bank_geometry(pcen, window, stride, n_fft, hop, row_floats, &geo, &bank, &nseg, &scan_lds);
+  if (rc != HONK_OK) return rc;
+  TickPlan tp;
+  const int trc = make_tick_plan(geo, bank, pcen ? "pcen" : "mfcc", slots, n_slots, slot_ids, offsets, n_fed, window,
+                                 stride, pcen && geo.mode == MODE_OVERLAP ? row_floats : 0, window0, next,
+                                 (BankRec*)table, table_capacity, &tp);
+  if (trc != HONK_OK) return trc;
+  *plan = tp.p;
+  return HONK_OK;
+}
+
+// the tick of either front end: params null: MFCC (cols = n_dct), else PCEN (cols = n_mels)
+static int bank_tick(const honk_pcen_params_t* params, bool pcen, const int16_t* chunks_dev,
+                     const honk_bank_slot_t* slots, int64_t n_slots, const int64_t* slot_ids, const int64_t* offsets,
+                     int64_t n_fed, const void* table_dev, size_t table_bytes, void* state_dev, size_t state_bytes,
+                     int32_t window, int32_t stride, const float* window_tbl, int32_t n_fft, int32_t hop,
+                     const float* mel_weights, int32_t n_mels, const float* dct, int32_t n_dct, float* out,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = pcen ? "pcen" : "mfcc";
+  if (!pcen && (n_mels < 1 || n_dct < 1)) return fail(HONK_ERR_ARG, "bad mfcc arguments");
+  const int cols = pcen ? n_mels : n_dct;
+  Plan geo;
+  BankPlan bank;
+  ScanArgs sa;
+  size_t scan_lds = 0;
+  const int rc = bank_geometry(pcen, window, stride, n_fft, hop, cols, &geo, &bank, &sa.nseg, &scan_lds);
+  if (rc != HONK_OK) return rc;
+  pcen::Params p;
+  int power = 0;
+  if (pcen) {
+    const int prc = pcen::check_params(params, &p, &power);
+    if (prc != HONK_OK) return prc;
+  }
+  TickPlan tp;
+  const int trc = make_tick_plan(geo, bank, who, slots, n_slots, slot_ids, offsets, n_fed, window, stride,
+                                 pcen && geo.mode == MODE_OVERLAP ? n_mels : 0, nullptr, nullptr, nullptr, 0, &tp);
+  if (trc != HONK_OK) return trc;
+  if (tp.p.samples_in == 0) return HONK_OK;  // (no new sample: no window, no tail moves)
+  if (!chunks_dev || !table_dev || !state_dev || !workspace) return fail(HONK_ERR_ARG, "null pointer argument");
+  const int64_t nw = tp.p.windows;
+  if (nw > 0 && (!window_tbl || !mel_weights || (!pcen && !dct) || !out))
+    return fail(HONK_ERR_ARG, "null pointer argument");
+  if (n_mels > MAX_MELS) return fail(HONK_ERR_UNSUPPORTED, "%s bank tick: more than %d mel bands", who, MAX_MELS);
+  if (workspace_bytes < (size_t)tp.p.workspace_bytes)
+    return fail(HONK_ERR_WORKSPACE, "%s bank tick workspace: %zu bytes, %lld needed", who, workspace_bytes,
+                (long long)tp.p.workspace_bytes);
+  if (table_bytes < (size_t)tp.p.table_bytes)
+    return fail(HONK_ERR_WORKSPACE, "%s bank tick table: %zu bytes, %lld needed", who, table_bytes,
+                (long long)tp.p.table_bytes);
+  if (state_bytes / (size_t)bank.p.slot_bytes < (size_t)n_slots)
+    return fail(HONK_ERR_WORKSPACE, "%s bank tick state: %zu bytes, %lld slots of %lld needed", who, state_bytes,
+                (long long)n_slots, (long long)bank.p.slot_bytes);
+  BankGeo bg = bank.geo;
+  bg.state = (char*)state_dev;
+  const BankRec* table = (const BankRec*)table_dev;
+  int16_t* pcm = (int16_t*)((char*)workspace + tp.pcm_offset);
+  float* erows = (float*)((char*)workspace + 2 * MAX_MELS * sizeof(int));
+  Args a;
+  size_t lds = 0;
+  if (nw > 0) {
+    // the layout is checked before anything is enqueued: a refused tick moves no tail
+    a.pcm = pcm; a.window = window_tbl; a.melw = mel_weights; a.dct = pcen ? nullptr : dct;
+    a.mrange = (const int*)workspace;
+    a.out = pcen && geo.mode == MODE_OVERLAP ? erows : out;
+    a.n_mels = n_mels; a.n_dct = pcen ? 0 : n_dct;
+    SegPlan sp;
+    sp.p = honk_mfcc_segments_plan_t{};
+    sp.p.windows = nw;
+    sp.p.shared_frames = tp.shared_rows;
+    sp.seg_tiles = tp.seg_tiles;
+    // the log-mel and output tiles and the slots' destination tables reuse the span area
+    const int tail_floats = pcen ? FT * (n_mels + 1) + 4 * FT : FT * (n_mels + 1) + FT * (n_dct + 1) + 5 * FT;
+    const int lrc = segments_layout(geo, sp, who, window, stride, n_fft, hop, tail_floats, nullptr, n_fed, &a, &lds);
+    if (lrc != HONK_OK) return lrc;
+    a.btable = table;
+    a.bank = bg;
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 copy_grid((unsigned)n_fed, (unsigned)std::max<int64_t>(1, std::min<int64_t>(BANK_MAX_Y, cdiv(tp.max_len, 4 * BANK_THREADS))));
+  hipLaunchKernelGGL(bank_assemble_kernel, copy_grid, dim3(BANK_THREADS), 0, st, table, bg, chunks_dev, pcm);
+  HONK_LAUNCH_CHECK("bank_assemble_kernel");
+  if (nw > 0) {
+    hipLaunchKernelGGL(mel_range_kernel, dim3((unsigned)n_mels), dim3(64), 0, st, mel_weights, a.n_bins,
+                       (int*)workspace);
+    HONK_LAUNCH_CHECK("mel_range_kernel");
+    const void* k1 = !pcen ? (const void*)mfcc_windows_kernel<EPI_MFCC, SRC_BANK>
+                           : power == 1 ? (const void*)mfcc_windows_kernel<EPI_PCEN1, SRC_BANK>
+                                        : (const void*)mfcc_windows_kernel<EPI_PCEN2, SRC_BANK>;
+    if (lds > 64 * 1024)
+      HONK_HIP_CHECK(hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const dim3 grid((unsigned)tp.p.tiles), block(64 * WAVES);
+    if (!pcen)
+      hipLaunchKernelGGL((mfcc_windows_kernel<EPI_MFCC, SRC_BANK>), grid, block, lds, st, a);
+    else if (power == 1)
+      hipLaunchKernelGGL((mfcc_windows_kernel<EPI_PCEN1, SRC_BANK>), grid, block, lds, st, a);
+    else
+      hipLaunchKernelGGL((mfcc_windows_kernel<EPI_PCEN2, SRC_BANK>), grid, block, lds, st, a);
+    HONK_LAUNCH_CHECK("mfcc_windows_kernel (bank tick)");
+    if (pcen) {
+      sa.e = erows; sa.out = out; sa.G = a.G; sa.table = nullptr; sa.n_rec = n_fed;
+      sa.frames = a.frames; sa.n_mels = n_mels; sa.flo = geo.flo; sa.fhi = geo.fhi; sa.q = geo.q; sa.mode = geo.mode;
+      if (geo.mode == MODE_OVERLAP) {
+        sa.btable = table;
+        sa.bank = bg;
+      }
+      if (scan_lds > 64 * 1024)
+        HONK_HIP_CHECK(hipFuncSetAttribute((const void*)pcen_windows_scan_kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      hipLaunchKernelGGL(pcen_windows_scan_kernel, dim3((unsigned)nw), dim3(SCAN_THREADS), scan_lds, st, sa, p);
+      HONK_LAUNCH_CHECK("pcen_windows_scan_kernel");
+    }
+    if (bank.p.cache_rows > 0) {
+      hipLaunchKernelGGL(bank_cache_kernel, dim3((unsigned)n_fed, (unsigned)cdiv(bank.p.cache_rows, FT)),
+                         dim3(BANK_THREADS), 0, st, table, bg, pcen ? nullptr : out, cols, geo.p.frames, geo.flo,
+                         geo.q);
+      HONK_LAUNCH_CHECK("bank_cache_kernel");
+    }
+  }
+  hipLaunchKernelGGL(bank_tail_kernel, copy_grid, dim3(BANK_THREADS), 0, st, table, bg, (const int16_t*)pcm);
+  HONK_LAUNCH_CHECK("bank_tail_kernel");
+  return HONK_OK;
+}
+
 }  // namespace mfccs
 }  // namespace honk
 
@@ -793,9 +1209,9 @@ extern "C" int honk_mfcc_segments_i16(const int16_t* pcm_i16, int64_t total_samp
                      (int*)workspace);
   HONK_LAUNCH_CHECK("mel_range_kernel");
   if (lds > 64 * 1024)
-    HONK_HIP_CHECK(hipFuncSetAttribute((const void*)mfcc_windows_kernel<EPI_MFCC, true>,
+    HONK_HIP_CHECK(hipFuncSetAttribute((const void*)mfcc_windows_kernel<EPI_MFCC, SRC_SEG>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL((mfcc_windows_kernel<EPI_MFCC, true>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds,
+  hipLaunchKernelGGL((mfcc_windows_kernel<EPI_MFCC, SRC_SEG>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds,
                      (hipStream_t)stream, a);
   HONK_LAUNCH_CHECK("mfcc_windows_kernel (segments)");
   return HONK_OK;
@@ -863,14 +1279,14 @@ extern "C" int honk_pcen_segments_i16(const int16_t* pcm_i16, int64_t total_samp
   hipLaunchKernelGGL(mel_range_kernel, dim3((unsigned)n_mels), dim3(64), 0, st, mel_weights, a.n_bins,
                      (int*)workspace);
   HONK_LAUNCH_CHECK("mel_range_kernel");
-  const void* k1 = power == 1 ? (const void*)mfcc_windows_kernel<EPI_PCEN1, true>
-                              : (const void*)mfcc_windows_kernel<EPI_PCEN2, true>;
+  const void* k1 = power == 1 ? (const void*)mfcc_windows_kernel<EPI_PCEN1, SRC_SEG>
+                              : (const void*)mfcc_windows_kernel<EPI_PCEN2, SRC_SEG>;
   if (lds > 64 * 1024)
     HONK_HIP_CHECK(hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   if (power == 1)
-    hipLaunchKernelGGL((mfcc_windows_kernel<EPI_PCEN1, true>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds, st, a);
+    hipLaunchKernelGGL((mfcc_windows_kernel<EPI_PCEN1, SRC_SEG>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds, st, a);
   else
-    hipLaunchKernelGGL((mfcc_windows_kernel<EPI_PCEN2, true>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds, st, a);
+    hipLaunchKernelGGL((mfcc_windows_kernel<EPI_PCEN2, SRC_SEG>), dim3((unsigned)sp.p.tiles), dim3(64 * WAVES), lds, st, a);
   HONK_LAUNCH_CHECK("mfcc_windows_kernel (segments, pcen energies)");
   if (scan_lds > 64 * 1024)
     HONK_HIP_CHECK(hipFuncSetAttribute((const void*)pcen_windows_scan_kernel,
@@ -878,4 +1294,65 @@ extern "C" int honk_pcen_segments_i16(const int16_t* pcm_i16, int64_t total_samp
   hipLaunchKernelGGL(pcen_windows_scan_kernel, dim3((unsigned)sp.p.windows), dim3(SCAN_THREADS), scan_lds, st, sa, p);
   HONK_LAUNCH_CHECK("pcen_windows_scan_kernel");
   return HONK_OK;
+}
+
+extern "C" int honk_stream_bank_plan(int32_t window, int32_t stride, int32_t n_fft, int32_t hop, int32_t row_floats,
+                                     honk_stream_bank_plan_t* plan) {
+  using namespace mfccs;
+  if (!plan) return fail(HONK_ERR_ARG, "null pointer argument");
+  if (row_floats < 1) return fail(HONK_ERR_ARG, "stream bank: row_floats < 1");
+  Plan geo;
+  const int rc = make_plan(0, window, stride, n_fft, hop, 0, 0, &geo);
+  if (rc != HONK_OK) return rc;
+  Args a;
+  int64_t tiles;
+  size_t lds;
+  const int lrc = layout(geo, "stream bank", window, stride, 0, 0, n_fft, hop, 0, &a, &tiles, &lds);
+  if (lrc != HONK_OK) return lrc;
+  BankPlan bank;
+  make_bank_plan(geo, window, row_floats, &bank);
+  *plan = bank.p;
+  return HONK_OK;
+}
+
+extern "C" int honk_mfcc_bank_tick_plan(const honk_bank_slot_t* slots, int64_t n_slots, const int64_t* slot_ids,
+                                        const int64_t* chunk_offsets, int64_t n_fed, int32_t window, int32_t stride,
+                                        int32_t n_fft, int32_t hop, int32_t n_dct, int64_t* window0,
+                                        honk_bank_slot_t* next, void* table, size_t table_capacity,
+                                        honk_bank_tick_plan_t* plan) {
+  return mfccs::bank_tick_plan(false, slots, n_slots, slot_ids, chunk_offsets, n_fed, window, stride, n_fft, hop, n_dct,
+                               window0, next, table, table_capacity, plan);
+}
+
+extern "C" int honk_pcen_bank_tick_plan(const honk_bank_slot_t* slots, int64_t n_slots, const int64_t* slot_ids,
+                                        const int64_t* chunk_offsets, int64_t n_fed, int32_t window, int32_t stride,
+                                        int32_t n_fft, int32_t hop, int32_t n_mels, int64_t* window0,
+                                        honk_bank_slot_t* next, void* table, size_t table_capacity,
+                                        honk_bank_tick_plan_t* plan) {
+  return mfccs::bank_tick_plan(true, slots, n_slots, slot_ids, chunk_offsets, n_fed, window, stride, n_fft, hop, n_mels,
+                               window0, next, table, table_capacity, plan);
+}
+
+extern "C" int honk_mfcc_bank_tick_i16(const int16_t* chunks_dev, const honk_bank_slot_t* slots, int64_t n_slots,
+                                       const int64_t* slot_ids, const int64_t* chunk_offsets, int64_t n_fed,
+                                       const void* table_dev, size_t table_bytes, void* state_dev, size_t state_bytes,
+                                       int32_t window, int32_t stride, const float* window_tbl, int32_t n_fft,
+                                       int32_t hop, const float* mel_weights, int32_t n_mels, const float* dct,
+                                       int32_t n_dct, float* out, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  return mfccs::bank_tick(nullptr, false, chunks_dev, slots, n_slots, slot_ids, chunk_offsets, n_fed, table_dev,
+                          table_bytes, state_dev, state_bytes, window, stride, window_tbl, n_fft, hop, mel_weights,
+                          n_mels, dct, n_dct, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int honk_pcen_bank_tick_i16(const int16_t* chunks_dev, const honk_bank_slot_t* slots, int64_t n_slots,
+                                       const int64_t* slot_ids, const int64_t* chunk_offsets, int64_t n_fed,
+                                       const void* table_dev, size_t table_bytes, void* state_dev, size_t state_bytes,
+                                       int32_t window, int32_t stride, const float* window_tbl, int32_t n_fft,
+                                       int32_t hop, const float* mel_weights, int32_t n_mels,
+                                       const honk_pcen_params_t* params, float* out, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  return mfccs::bank_tick(params, true, chunks_dev, slots, n_slots, slot_ids, chunk_offsets, n_fed, table_dev,
+                          table_bytes, state_dev, state_bytes, window, stride, window_tbl, n_fft, hop, mel_weights,
+                          n_mels, nullptr, 0, out, workspace, workspace_bytes, stream);
 }

@@ -9,6 +9,7 @@ batched form (every window of a request in one forward).
 from __future__ import annotations
 
 import os
+import warnings
 import wave
 
 import numpy as np
@@ -299,20 +300,51 @@ class StreamPool(object):
     ``StreamListener`` fed the same bytes returns.  A key is opened at its first feed; ``close(key)`` drops
     its tail.  Per tick the streams that complete at least one window go through ONE
     ``service.label_streams`` call (one upload, one front-end call, one forward, one download), whatever
-    their number.  Tails stay on the host, as a ``StreamListener``'s."""
+    their number.  Tails stay on the host, as a ``StreamListener``'s.
 
-    def __init__(self, service, stride_size_ms=500):
+    ``device_state=True`` (a ROCm service, an even stride in bytes): a key owns a slot of a
+    ``StreamBank`` instead -- its tail and the finished rows its next window reuses stay on the device.
+    ``feed`` uploads only the fed bytes and runs one bank tick, the forward in slices of at most 8192
+    windows, one softmax and one download.  A chunk that ends mid-sample leaves its odd byte on the host, in
+    front of that key's next chunk.  Where the bank cannot be built (a CPU service, an odd stride in bytes,
+    a shape its plan refuses) the pool warns once and works as with ``device_state=False``."""
+
+    MAX_WINDOWS = 8192
+
+    def __init__(self, service, stride_size_ms=500, device_state=False):
         self.service = service
         self.stride_size_ms = stride_size_ms
         self._streams = {}
+        self.bank = self._make_bank() if device_state else None
+
+    def _make_bank(self):
+        svc = self.service
+        stride_bytes = int(2 * 16000 * self.stride_size_ms / 1000)
+        why = None
+        if svc.no_cuda:
+            why = "the service runs on the CPU"
+        elif stride_bytes < 2 or stride_bytes % 2:
+            why = f"a stride of {stride_bytes} bytes is no whole number of samples"
+        else:
+            try:
+                return svc.audio_processor.stream_bank(stride_bytes // 2, 16000, svc.audio_preprocess_type,
+                                                       next(svc.model.parameters()).device)
+            except ValueError as e:
+                why = str(e)
+        warnings.warn(f"StreamPool: device_state=True not available ({why}); tails stay on the host")
+        return None
 
     def keys(self):
         return list(self._streams)
 
     def close(self, key):
-        self._streams.pop(key, None)
+        st = self._streams.pop(key, None)
+        if self.bank is not None and st is not None:
+            self.bank.close(st[0])
 
     def feed(self, chunks):
+        if self.bank is not None:
+            return self._feed_bank(chunks)
         out, ready = {}, []
         for key, wav_bytes in chunks.items():
             sl = self._streams.get(key)
@@ -327,6 +359,32 @@ class StreamPool(object):
             for (key, sl, _), got in zip(ready, labelled):
                 sl._pop(len(got))
                 out[key] = got
+        return out
+
+    def _feed_bank(self, chunks):
+        """One tick on the bank: a stream is [slot, the odd byte of its last chunk]."""
+        svc, out, ids, parts = self.service, {}, [], []
+        for key, wav_bytes in chunks.items():
+            st = self._streams.get(key)
+            if st is None:
+                st = self._streams[key] = [self.bank.open(), b""]
+            data = st[1] + bytes(wav_bytes)
+            n = len(data) // 2
+            st[1] = data[2 * n:]
+            out[key] = []
+            ids.append(st[0])
+            parts.append(np.frombuffer(data, dtype=np.int16, count=n))
+        if not ids:
+            return out
+        off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
+        x, w0 = self.bank.tick(ids, torch.from_numpy(np.concatenate(parts)), off)
+        if x.shape[0]:
+            with torch.no_grad():
+                net = svc._net()
+                logits = torch.cat([net(x[a:a + self.MAX_WINDOWS]) for a in range(0, x.shape[0], self.MAX_WINDOWS)])
+                p = F.softmax(logits.cpu(), dim=1).numpy()
+            for j, key in enumerate(chunks):
+                out[key] = [(svc.labels[int(np.argmax(r))], float(np.max(r))) for r in p[w0[j]:w0[j + 1]]]
         return out
 
 

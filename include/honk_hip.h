@@ -653,6 +653,113 @@ int honk_pcen_segments_i16(const int16_t* pcm_i16, int64_t total_samples, const 
                            int32_t n_mels, const honk_pcen_params_t* params /* NULL = defaults */,
                            float* out /* [sum W_r][1 + window/hop][n_mels] */,
                            void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * A stream bank: the segments calls for a server that listens tick after tick, with each
+ * stream's unconsumed samples and the finished rows its next window reuses kept on the device
+ * between ticks.  A tick takes only the NEW samples of the streams fed in it.
+ *
+ * Stream k has received x_k[0, N) and emitted E windows (window w = x_k[w stride, w stride +
+ * window)).  A tick feeds c >= 0 samples: N' = N + c, E' = N' < window ? 0 : 1 + (N' - window) /
+ * stride.  The tick's rows for the stream are, bit for bit, rows [E, E') of
+ * honk_mfcc_windows_i16 (honk_pcen_windows_i16) on x_k[0, N') in a buffer of its own, whatever
+ * the chunking, the other streams of the tick and the order of the slots: a frame's row is a
+ * function of its own n_fft samples alone, in a fixed order, and the per-frame code is the same.
+ *
+ * Device state: n_slots * slot_bytes bytes of caller memory (state_dev), opaque to the caller;
+ * a slot is [tail: at most window - 1 int16][two halves of cache_rows rows of row_floats
+ * floats].  Host bookkeeping: one honk_bank_slot_t per slot, held by the caller; a slot is
+ * opened (or reused) by zeroing its struct -- the device bytes need no initialisation.
+ *   tail    samples in the slot: x_k[E stride, N) (stride > window: empty while E stride > N)
+ *   skip    stride > window: the E stride - N samples still to come before the next window's
+ *           start.  The CALLER drops them from later chunks before the upload and decrements
+ *           skip; a tick that feeds samples to a slot with skip > 0 is refused
+ *   cached  rows in the cache: 0 until the stream has emitted a window, then cache_rows
+ *   parity  the cache half that holds them (a tick that completes a window writes the other)
+ * The cache exists on the overlapping shared route only (stride % hop == 0 and q = stride / hop
+ * <= fhi - flo, [flo, fhi] the interior frames): cache_rows = fhi - flo + 1 - q, row i the
+ * interior frame flo + i of the stream's NEXT window (MFCC: its finished n_dct values; PCEN:
+ * its n_mels mel energies before the smoother, which still restarts per window).  On the gapped
+ * and unshared routes cache_rows = 0 and the bank saves only the upload.
+ *
+ * honk_stream_bank_plan (host-only): the slot geometry for row_floats floats per row (n_dct;
+ * PCEN: n_mels); route 0 unshared, 1 overlapping, 2 gapped.
+ *
+ * honk_*_bank_tick_plan (host-only): slots [n_slots] the states before the tick, slot_ids
+ * [n_fed] the fed slots (distinct, any order), chunk_offsets [n_fed + 1] (nondecreasing, >= 0)
+ * locating each fed stream's new samples in chunks_dev.  Fills window0 [n_fed + 1] (rows
+ * [window0[r], window0[r+1]) of out are fed stream r's; may be NULL), next [n_fed] (the fed
+ * slots' states after the tick, for the caller to commit once the tick is enqueued; may be NULL),
+ * the table (host memory of table_capacity bytes for the caller to copy to table_dev; NULL:
+ * sizes only) and the counts.  A refused tick writes none of them.  A stream that completes
+ * n >= 1 windows computes the frames jl >= flo + cached of its virtual window (n q in steady
+ * state) and 2 (flo + frames - 1 - fhi) edge frames per window, and takes `cached` rows from
+ * the cache: frames_computed and frames_reused are the sums.
+ *
+ * honk_*_bank_tick_i16 take the same slots / slot_ids / chunk_offsets again (re-validated) and
+ * only enqueue on `stream`: no synchronisation, no device allocation, no copy by the host.
+ * Launches: assemble "tail | chunk" per fed stream in the workspace; the frame-tile kernel
+ * over the fed streams (a finished row the next window reuses also goes to the slot's other
+ * cache half); PCEN's scan per window (cached rows, the tick's rows, the window's edge rows);
+ * the cached rows' fan-out to out and their move to the other half; the new tails from the
+ * workspace to the slots.  Within a launch no location is read by one workgroup and written by
+ * another.  NOT meant for graph capture: the host bookkeeping, the table and the grid change
+ * with every tick.
+ * n_fed == 0 or no new sample: HONK_OK, nothing enqueued; new samples but no window: HONK_OK,
+ * the tails advance (out may be NULL).  Status: HONK_ERR_ARG (a null pointer, a negative count,
+ * offsets that decrease or are negative, a slot id out of range or fed twice, a slot state no
+ * tick can have left, samples for a slot with skip > 0, and the shape / PCEN parameter refusals
+ * of the segments calls); HONK_ERR_WORKSPACE (a short table, workspace or state_dev);
+ * HONK_ERR_UNSUPPORTED (exactly the shapes the segments calls refuse).  The shape and the
+ * parameters are checked first.  Memory contract: out is fully written and nothing outside
+ * it; only [0, workspace_bytes) of the workspace is touched and its contents on entry are
+ * ignored; chunks_dev and table_dev are never modified; in state_dev only bytes of the fed
+ * slots change.
+ */
+typedef struct honk_bank_slot_t { int32_t tail, cached, skip, parity; } honk_bank_slot_t;
+typedef struct honk_stream_bank_plan_t {
+  int64_t slot_bytes;       /* bytes of state_dev per slot                                  */
+  int32_t tail_capacity;    /* window - 1                                                   */
+  int32_t cache_rows;       /* fhi - flo + 1 - q on the overlapping route, else 0           */
+  int32_t route, frames, row_floats, flo, fhi, q;
+} honk_stream_bank_plan_t;
+typedef struct honk_bank_tick_plan_t {
+  int64_t windows;          /* sum over the fed streams: rows of out                        */
+  int64_t frames_computed, frames_reused, edge_frames;
+  int64_t tiles;            /* workgroups of the frame-tile kernel                          */
+  int64_t workspace_bytes, table_bytes;
+  int64_t samples_in;       /* chunk_offsets[n_fed] - chunk_offsets[0]                      */
+} honk_bank_tick_plan_t;
+int honk_stream_bank_plan(int32_t window, int32_t stride, int32_t n_fft, int32_t hop, int32_t row_floats,
+                          honk_stream_bank_plan_t* plan);
+int honk_mfcc_bank_tick_plan(const honk_bank_slot_t* slots, int64_t n_slots, const int64_t* slot_ids,
+                             const int64_t* chunk_offsets, int64_t n_fed, int32_t window, int32_t stride,
+                             int32_t n_fft, int32_t hop, int32_t n_dct,
+                             int64_t* window0 /* host [n_fed+1], may be NULL */,
+                             honk_bank_slot_t* next /* host [n_fed], may be NULL */,
+                             void* table /* host, may be NULL: sizes only */, size_t table_capacity,
+                             honk_bank_tick_plan_t* plan);
+int honk_pcen_bank_tick_plan(const honk_bank_slot_t* slots, int64_t n_slots, const int64_t* slot_ids,
+                             const int64_t* chunk_offsets, int64_t n_fed, int32_t window, int32_t stride,
+                             int32_t n_fft, int32_t hop, int32_t n_mels,
+                             int64_t* window0 /* host [n_fed+1], may be NULL */,
+                             honk_bank_slot_t* next /* host [n_fed], may be NULL */,
+                             void* table /* host, may be NULL: sizes only */, size_t table_capacity,
+                             honk_bank_tick_plan_t* plan);
+int honk_mfcc_bank_tick_i16(const int16_t* chunks_dev, const honk_bank_slot_t* slots, int64_t n_slots,
+                            const int64_t* slot_ids, const int64_t* chunk_offsets, int64_t n_fed,
+                            const void* table_dev, size_t table_bytes, void* state_dev, size_t state_bytes,
+                            int32_t window, int32_t stride, const float* window_tbl, int32_t n_fft, int32_t hop,
+                            const float* mel_weights, int32_t n_mels, const float* dct, int32_t n_dct,
+                            float* out /* [windows][1 + window/hop][n_dct] */,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int honk_pcen_bank_tick_i16(const int16_t* chunks_dev, const honk_bank_slot_t* slots, int64_t n_slots,
+                            const int64_t* slot_ids, const int64_t* chunk_offsets, int64_t n_fed,
+                            const void* table_dev, size_t table_bytes, void* state_dev, size_t state_bytes,
+                            int32_t window, int32_t stride, const float* window_tbl, int32_t n_fft, int32_t hop,
+                            const float* mel_weights, int32_t n_mels,
+                            const honk_pcen_params_t* params /* NULL = defaults */,
+                            float* out /* [windows][1 + window/hop][n_mels] */,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training (data-parallel train(), utils/train.py:99-135) -------------------- */
 /*
