@@ -435,7 +435,9 @@ class AudioPreprocessor(object):
         """A ``StreamBank`` of this front end: ``compute_mfccs_segments`` (``front="PCEN"``:
         ``compute_pcen_segments``) for streams that arrive in chunks, fed only their new samples.
         device None: the current ROCm device where there is one, else the CPU.  A shape the plan refuses
-        raises ValueError."""
+        raises ValueError, and on a ROCm device so does a shape a tick would refuse (the mel bands of an MFCC
+        bank, the frame-tile kernel's LDS plan): the constructor asks honk_*_bank_tick_i16 itself, with an
+        empty tick."""
         return StreamBank(self, stride, window, front, device, slots)
 
     def _windows_workspace(self, device, nbytes):
@@ -488,6 +490,10 @@ class StreamBank(object):
                                        ctypes.addressof(self.plan))
         if rc == 0:  # the front end's own refusals (PCEN: the mel bands, stage 2's tile)
             rc = self._plan(np.zeros(0, np.int64), np.zeros(1, np.int64), np.zeros(1, _native.BANK_SLOT_DTYPE))[0]
+        if rc == 0 and self.device.type != "cpu":
+            # what only the tick itself knows (the mel bands of an MFCC bank, the frame-tile kernel's LDS plan
+            # with its epilogue and group table): an empty tick checks the shape and enqueues nothing
+            rc = self._empty_tick()
         if rc != 0:
             raise ValueError("stream_bank: " + lib.honk_last_error().decode(errors="replace"))
         self.route = _native.BANK_ROUTES[self.plan.route]
@@ -498,6 +504,20 @@ class StreamBank(object):
         self._state = None
         if self.device.type != "cpu":
             self._state = torch.empty(int(slots) * int(self.plan.slot_bytes), dtype=torch.uint8, device=self.device)
+
+    def _empty_tick(self):
+        """honk_*_bank_tick_i16 with no fed stream -> status: the shape checks of a tick and nothing else (no
+        pointer is read, nothing is enqueued); host-only."""
+        from . import _native
+        ap, lib = self.ap, _native.load()
+        off = np.zeros(1, np.int64)
+        head = (None, None, 0, None, off.ctypes.data, 0, None, 0, None, 0, self.window, self.stride, None, ap.n_fft,
+                ap.hop_length, None, ap._mel.shape[0])
+        if self.pcen:
+            p = ap.pcen_params
+            params = _native.PcenParams(p["eps"], p["s"], p["alpha"], p["delta"], p["r"], int(p["power"]))
+            return lib.honk_pcen_bank_tick_i16(*head, ctypes.addressof(params), None, None, 0, None)
+        return lib.honk_mfcc_bank_tick_i16(*head, None, self.cols, None, None, 0, None)
 
     @property
     def slots(self):

@@ -946,12 +946,28 @@ static int bank_tick(const honk_pcen_params_t* params, bool pcen, const int16_t*
   const int trc = make_tick_plan(geo, bank, who, slots, n_slots, slot_ids, offsets, n_fed, window, stride,
                                  pcen && geo.mode == MODE_OVERLAP ? n_mels : 0, nullptr, nullptr, nullptr, 0, &tp);
   if (trc != HONK_OK) return trc;
+  // the shape's own refusals (the mel-range table, the frame-tile kernel's LDS plan) come before the counts
+  // are looked at: an empty tick -- no launch, no state touched -- tells a caller at construction whether any
+  // later tick of the shape would be refused
+  if (n_mels > MAX_MELS) return fail(HONK_ERR_UNSUPPORTED, "%s bank tick: more than %d mel bands", who, MAX_MELS);
+  const int64_t nw = tp.p.windows;
+  Args a;
+  size_t lds = 0;
+  {
+    SegPlan sp;
+    sp.p = honk_mfcc_segments_plan_t{};
+    sp.p.windows = nw;
+    sp.p.shared_frames = tp.shared_rows;
+    sp.seg_tiles = tp.seg_tiles;
+    // the log-mel and output tiles and the slots' destination tables reuse the span area
+    const int tail_floats = pcen ? FT * (n_mels + 1) + 4 * FT : FT * (n_mels + 1) + FT * (n_dct + 1) + 5 * FT;
+    const int lrc = segments_layout(geo, sp, who, window, stride, n_fft, hop, tail_floats, nullptr, n_fed, &a, &lds);
+    if (lrc != HONK_OK) return lrc;
+  }
   if (tp.p.samples_in == 0) return HONK_OK;  // (no new sample: no window, no tail moves)
   if (!chunks_dev || !table_dev || !state_dev || !workspace) return fail(HONK_ERR_ARG, "null pointer argument");
-  const int64_t nw = tp.p.windows;
   if (nw > 0 && (!window_tbl || !mel_weights || (!pcen && !dct) || !out))
     return fail(HONK_ERR_ARG, "null pointer argument");
-  if (n_mels > MAX_MELS) return fail(HONK_ERR_UNSUPPORTED, "%s bank tick: more than %d mel bands", who, MAX_MELS);
   if (workspace_bytes < (size_t)tp.p.workspace_bytes)
     return fail(HONK_ERR_WORKSPACE, "%s bank tick workspace: %zu bytes, %lld needed", who, workspace_bytes,
                 (long long)tp.p.workspace_bytes);
@@ -966,23 +982,11 @@ static int bank_tick(const honk_pcen_params_t* params, bool pcen, const int16_t*
   const BankRec* table = (const BankRec*)table_dev;
   int16_t* pcm = (int16_t*)((char*)workspace + tp.pcm_offset);
   float* erows = (float*)((char*)workspace + 2 * MAX_MELS * sizeof(int));
-  Args a;
-  size_t lds = 0;
   if (nw > 0) {
-    // the layout is checked before anything is enqueued: a refused tick moves no tail
     a.pcm = pcm; a.window = window_tbl; a.melw = mel_weights; a.dct = pcen ? nullptr : dct;
     a.mrange = (const int*)workspace;
     a.out = pcen && geo.mode == MODE_OVERLAP ? erows : out;
     a.n_mels = n_mels; a.n_dct = pcen ? 0 : n_dct;
-    SegPlan sp;
-    sp.p = honk_mfcc_segments_plan_t{};
-    sp.p.windows = nw;
-    sp.p.shared_frames = tp.shared_rows;
-    sp.seg_tiles = tp.seg_tiles;
-    // the log-mel and output tiles and the slots' destination tables reuse the span area
-    const int tail_floats = pcen ? FT * (n_mels + 1) + 4 * FT : FT * (n_mels + 1) + FT * (n_dct + 1) + 5 * FT;
-    const int lrc = segments_layout(geo, sp, who, window, stride, n_fft, hop, tail_floats, nullptr, n_fed, &a, &lds);
-    if (lrc != HONK_OK) return lrc;
     a.btable = table;
     a.bank = bg;
   }

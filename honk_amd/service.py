@@ -307,7 +307,8 @@ class StreamPool(object):
     ``feed`` uploads only the fed bytes and runs one bank tick, the forward in slices of at most 8192
     windows, one softmax and one download.  A chunk that ends mid-sample leaves its odd byte on the host, in
     front of that key's next chunk.  Where the bank cannot be built (a CPU service, an odd stride in bytes,
-    a shape its plan refuses) the pool warns once and works as with ``device_state=False``."""
+    a shape its plan or its tick refuses: ``stream_bank`` raises ValueError for both at construction) the
+    pool warns once and works as with ``device_state=False``."""
 
     MAX_WINDOWS = 8192
 

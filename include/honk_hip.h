@@ -710,7 +710,12 @@ int honk_pcen_segments_i16(const int16_t* pcm_i16, int64_t total_samples, const 
  * tick can have left, samples for a slot with skip > 0, and the shape / PCEN parameter refusals
  * of the segments calls); HONK_ERR_WORKSPACE (a short table, workspace or state_dev);
  * HONK_ERR_UNSUPPORTED (exactly the shapes the segments calls refuse).  The shape and the
- * parameters are checked first.  Memory contract: out is fully written and nothing outside
+ * parameters are checked first, before the counts are looked at: that includes the two refusals
+ * no plan call above makes -- more than 128 mel bands (the MFCC plan calls take n_dct only) and
+ * the frame-tile kernel's LDS plan with the epilogue's tiles and the group table
+ * (honk_stream_bank_plan checks it without either).  So a tick with n_fed == 0 and every
+ * pointer NULL returns the status every later tick of the shape would: a caller issues it once
+ * when it builds the bank, and refuses the shape there.  Memory contract: out is fully written and nothing outside
  * it; only [0, workspace_bytes) of the workspace is touched and its contents on entry are
  * ignored; chunks_dev and table_dev are never modified; in state_dev only bytes of the fed
  * slots change.

@@ -158,6 +158,9 @@ WINDOWS = [
     WinCase("2048-16", 4000, 2048, 16, 40, 40, 3, "more than 32 edge frames per side: plan refusal, then fallback",
             kernel=False),
     WinCase("win300", 300, 480, 160, 40, 40, 9, "no interior frame: unshared at either stride", shared=False),
+    WinCase("800-160", 16000, 800, 160, 40, 40, 3, "3 edge frames per side: 10 groups per edge tile, FT % gs != 0"),
+    WinCase("1024-128", 8192, 1024, 128, 40, 40, 3, "4 edge frames per side, 65 frames"),
+    WinCase("win16240", 16240, 480, 160, 40, 40, 3, "2 head and 1 tail edge frame: 102 frames, fhi = 100"),
 ]
 WIN_BY_ID = {c.id: c for c in WINDOWS}
 

@@ -62,49 +62,53 @@ CASES = {
 }
 
 
-def streams(name):
+# The helpers below take the shape by keyword -- window, hop, the interior frames [flo, fhi], frames and cols
+# of a row, seed, and case: a (stride, ticks) schedule that is not in CASES -- with the reference shape the
+# schedules above are written for as the default.  tests/stream_geometry_cases.py has the shapes off it.
+def streams(name, case=None):
     """{stream: total samples} in order of first appearance."""
     total = {}
-    for feed, _, _ in CASES[name][1]:
+    for feed, _, _ in (CASES[name] if case is None else case)[1]:
         for k, n in feed:
             total[k] = total.get(k, 0) + n
     return total
 
 
-def recordings(name):
-    return {k: _pcm(SEED + i, n) for i, (k, n) in enumerate(streams(name).items())}
+def recordings(name, case=None, seed=SEED):
+    return {k: _pcm(seed + i, n) for i, (k, n) in enumerate(streams(name, case).items())}
 
 
-def cache_rows(stride):
+def cache_rows(stride, hop=HOP, flo=FLO, fhi=FHI):
     """The issue's formula: fhi - flo + 1 - q on the overlapping route, else 0."""
-    q = stride // HOP
-    return NINT - q if stride % HOP == 0 and q <= FHI - FLO else 0
+    q = stride // hop
+    return fhi - flo + 1 - q if stride % hop == 0 and q <= fhi - flo else 0
 
 
 class Model:
     """The issue's arithmetic for one stream, written from the definitions: N samples received, E windows
     emitted."""
 
-    def __init__(self, stride):
+    def __init__(self, stride, window=WIN, hop=HOP, flo=FLO, fhi=FHI, frames=FRAMES):
         self.stride, self.N, self.E = stride, 0, 0
-        self.rows = cache_rows(stride)
-        self.shared = stride % HOP == 0
-        self.overlap = self.shared and stride // HOP <= FHI - FLO
+        self.window, self.hop, self.nint, self.frames = window, hop, fhi - flo + 1, frames
+        self.rows = cache_rows(stride, hop, flo, fhi)
+        self.shared = stride % hop == 0
+        self.overlap = self.shared and stride // hop <= fhi - flo
 
     def cached(self):
         return self.rows if self.E > 0 else 0
 
     def feed(self, c):
         """-> (n windows, frames_computed, frames_reused) of the tick; advances the stream."""
-        cached, q = self.cached(), self.stride // HOP
+        cached, q = self.cached(), self.stride // self.hop
         self.N += c
-        E = 0 if self.N < WIN else 1 + (self.N - WIN) // self.stride
+        E = 0 if self.N < self.window else 1 + (self.N - self.window) // self.stride
         n, self.E = E - self.E, E
         if n == 0:
             return 0, 0, 0
         if self.overlap:
-            return n, (n - 1) * q + NINT - cached + n * (FRAMES - NINT), cached
-        return n, n * FRAMES, 0
+            return n, (n - 1) * q + self.nint - cached + n * (self.frames - self.nint), cached
+        return n, n * self.frames, 0
 
     def state(self):
         """(tail, cached, skip)."""
@@ -112,13 +116,14 @@ class Model:
         return max(0, self.N - nxt), self.cached(), max(0, nxt - self.N)
 
 
-def run(ap, name, front, device, slots=2, only=None, reverse=False, before_tick=None):
+def run(ap, name, front, device, slots=2, only=None, reverse=False, before_tick=None, window=WIN, frames=FRAMES,
+        cols=40, case=None, seed=SEED):
     """Play a schedule on a fresh bank -> ({stream: its rows over the ticks, concatenated}, bank).
     only: feed these streams alone; reverse: every tick's feed order reversed; before_tick(bank, ids, pcm,
     off) -> a context manager around each tick (the memory-contract tests)."""
-    stride, ticks = CASES[name]
-    bank = ap.stream_bank(stride, WIN, front, device, slots)
-    recs, pos, slot = recordings(name), {}, {}
+    stride, ticks = CASES[name] if case is None else case
+    bank = ap.stream_bank(stride, window, front, device, slots)
+    recs, pos, slot = recordings(name, case, seed), {}, {}
     rows = {}
     for feed, close, descending in ticks:
         feed = [(k, n) for k, n in feed if only is None or k in only]
@@ -137,7 +142,7 @@ def run(ap, name, front, device, slots=2, only=None, reverse=False, before_tick=
             x, w0 = bank.tick(ids, pcm, off)
         else:
             x, w0 = before_tick(bank, ids, pcm, off)
-        assert x.dtype == torch.float32 and x.shape[1:] == (FRAMES, 40) and x.device.type == torch.device(device).type
+        assert x.dtype == torch.float32 and x.shape[1:] == (frames, cols) and x.device.type == torch.device(device).type
         assert w0[0] == 0 and w0[-1] == x.shape[0]
         x = x.cpu().numpy()
         for j, (k, n) in enumerate(feed):
@@ -149,18 +154,18 @@ def run(ap, name, front, device, slots=2, only=None, reverse=False, before_tick=
     return {k: np.concatenate(v) for k, v in rows.items()}, bank
 
 
-def whole(ap, name, front, device):
+def whole(ap, name, front, device, window=WIN, case=None, seed=SEED):
     """{stream: compute_{mfccs,pcen}_windows of its whole recording in a buffer of its own}: what the
     ticks' rows must add up to, byte for byte."""
-    stride = CASES[name][0]
+    stride = (CASES[name] if case is None else case)[0]
     windows = ap.compute_pcen_windows if front == "PCEN" else ap.compute_mfccs_windows
-    return {k: windows(torch.from_numpy(np.ascontiguousarray(r)).to(device), stride).cpu().numpy()
-            for k, r in recordings(name).items()}
+    return {k: windows(torch.from_numpy(np.ascontiguousarray(r)).to(device), stride, window).cpu().numpy()
+            for k, r in recordings(name, case, seed).items()}
 
 
 def check(ap, name, front, device, **kw):
     got, bank = run(ap, name, front, device, **kw)
-    want = whole(ap, name, front, device)
+    want = whole(ap, name, front, device, **{k: kw[k] for k in ("window", "case", "seed") if k in kw})
     for k, rows in got.items():
         ref = want[k]
         assert rows.shape == ref.shape and len(ref) > 0 and rows.tobytes() == ref.tobytes(), (name, k)
@@ -212,15 +217,17 @@ def native_tick(arena, bank, ids, pcm, off, frozen):
     return out, w0
 
 
-def memory_contract(front, name, want, device, pu):
+def memory_contract(front, name, want, device, pu, preprocessor=None, **kw):
     """The schedule with the bank's state, every tick's out and workspace poisoned and guard-banded, for
-    every fill: the unpoisoned rows."""
+    every fill: the unpoisoned rows.  preprocessor: makes the front end of each fill (None: the default
+    one); kw: run()'s shape keywords."""
     from honk_amd.audio import AudioPreprocessor
     for fill in pu.FILLS:
         a = pu.arena(fill)
         with a:
-            got, bank = run(AudioPreprocessor(), name, front, device, slots=2,
-                            before_tick=lambda bank, ids, pcm, off: native_tick(a, bank, ids, pcm, off, pu.frozen))
+            got, bank = run((preprocessor or AudioPreprocessor)(), name, front, device, slots=2,
+                            before_tick=lambda bank, ids, pcm, off: native_tick(a, bank, ids, pcm, off, pu.frozen),
+                            **kw)
         a.check()
         assert set(got) == set(want)
         for k in got:
