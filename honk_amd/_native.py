@@ -257,6 +257,8 @@ _PROTOS = {
                                                c_f32p, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32,
                                                ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
                                                ctypes.c_void_p]),
+    "honk_listen_decide_f32": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "honk_spatial_mean_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_spatial_mean_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
     "honk_cross_entropy_f32": (ctypes.c_int, [c_f32p, ctypes.c_void_p, c_f32p, ctypes.c_int64, ctypes.c_int32,
@@ -435,6 +437,52 @@ def front_plan(samples, n_fft, hop, n_mels, n_dct=None):
     else:
         rc = lib.honk_mfcc_plan(int(samples), int(n_fft), int(hop), int(n_mels), int(n_dct), ctypes.addressof(plan))
     return rc, plan
+
+
+LISTEN_MAX_LABELS = 64        # HONK_LISTEN_MAX_LABELS
+LISTEN_MAX_WINDOWS = 1 << 23  # HONK_LISTEN_MAX_WINDOWS
+
+
+def listen_window0(window0, n, who="listen_decide"):
+    """A segment table as a contiguous int64 array: ``window0[0] == 0``, non-decreasing, last entry ``n``
+    (ValueError otherwise)."""
+    import numpy as np
+    w0 = np.asarray(window0)
+    if w0.ndim != 1 or w0.size < 1 or w0.dtype.kind not in "iu":
+        raise ValueError(f"{who}: window0 must be a 1-D integer array of segments + 1 entries")
+    w0 = np.ascontiguousarray(w0, dtype=np.int64)
+    if w0[0] != 0 or (np.diff(w0) < 0).any() or w0[-1] != n:
+        raise ValueError(f"{who}: window0 must start at 0, not decrease and end at {n}")
+    return w0
+
+
+def listen_decide(logits, window0=None, keyword=-1, min_prob=0.85):
+    """honk_listen_decide_f32 on a ROCm float32 tensor ``logits`` [n, n_labels] -> device tensors
+    ``(label int32 [n], prob float32 [n])``, and with ``window0`` (numpy int64 [segments + 1], checked here,
+    then uploaded) also ``(sums float64, counts int32 [segments, n_labels], hit int64 [segments])``.
+    Only enqueues on the current stream of the tensor's device."""
+    import torch
+    if not torch.is_tensor(logits) or not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError("listen_decide: logits must be a 2-D float32 tensor on a ROCm device")
+    n, n_labels = logits.shape
+    w0 = None if window0 is None else listen_window0(window0, n)
+    logits = logits.detach().contiguous()
+    dev = logits.device
+    label = torch.empty(n, dtype=torch.int32, device=dev)
+    prob = torch.empty(n, dtype=torch.float32, device=dev)
+    segments = 0 if w0 is None else w0.size - 1
+    w0_dev = sums = counts = hit = None
+    if w0 is not None:
+        w0_dev = torch.from_numpy(w0).to(dev)
+        sums = torch.empty(segments, n_labels, dtype=torch.float64, device=dev)
+        counts = torch.empty(segments, n_labels, dtype=torch.int32, device=dev)
+        hit = torch.empty(segments, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = load().honk_listen_decide_f32(ptr(logits), n, n_labels, ptr(w0_dev), segments, int(keyword),
+                                           float(min_prob), ptr(label), ptr(prob), ptr(sums), ptr(counts), ptr(hit),
+                                           stream_handle(dev))
+    check(rc, "honk_listen_decide_f32")
+    return (label, prob) if w0 is None else (label, prob, sums, counts, hit)
 
 
 def res_numerics(desc, packed, device):

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhonk_hip.so")
 SOURCES = ["runtime.cpp", "res.hip", "res_vf.hip", "cnn.hip", "train.hip", "mfcc.hip", "mfcc_stream.hip", "pcen.hip",
-           "head.hip", "augment.hip"]
+           "head.hip", "augment.hip", "listen.hip"]
 # per-source extra flags / dependencies: res_vf.hip (the f16x2 pair and last-layer kernels)
 # includes res.hip and takes the MFMA accumulators in VGPRs (see its header)
 FLAGS = {"res_vf.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}

@@ -24,6 +24,9 @@ def _softmax(x):
     return np.exp(x) / np.sum(np.exp(x))
 
 
+_NUMPY_OF = {torch.int32: np.int32, torch.int64: np.int64, torch.float32: np.float32, torch.float64: np.float64}
+
+
 class LabelService(object):
     def evaluate(self, speech_dirs, indices=[]):
         """service.py:32-50: accuracy of label() over folders of 1 s wav clips."""
@@ -74,18 +77,28 @@ class TorchLabelService(LabelService):
     among the windows of a recording as the MFCC path shares its frames (``compute_pcen_windows``).
 
     Many recordings at once: ``label_streams`` (one upload, one ragged-batch front-end call, one forward
-    and one download per batch of windows) and a ``StreamPool`` over it, under either front end."""
+    and one download per batch of windows) and a ``StreamPool`` over it, under either front end.
+
+    ``decide`` is the stage after the forward -- per window the label and its probability, per segment of
+    windows the summed probabilities, the counts and the first keyword hit -- as one native call
+    (honk_listen_decide_f32, csrc/listen.hip) and one small download; ``listen_streams`` answers a batch of
+    recordings from it.  ``honk_decide`` (opt-in, default False): ``label_batch``, ``label_stream``,
+    ``label_streams`` and a ``StreamPool`` take their (label, prob) from ``decide`` instead of downloading the
+    logits and running softmax / argmax / max row by row on the host."""
 
     honk_graph = False
     honk_latency = False
+    honk_decide = False
 
     def __init__(self, model_filename, no_cuda=False, labels=["_silence_", "_unknown_", "command", "random"],
-                 audio_processor=None, honk_graph=False, audio_preprocess_type="MFCCs", honk_latency=False):
+                 audio_processor=None, honk_graph=False, audio_preprocess_type="MFCCs", honk_latency=False,
+                 honk_decide=False):
         if audio_preprocess_type not in ("MFCCs", "PCEN"):
             raise ValueError(f"TorchLabelService: audio_preprocess_type {audio_preprocess_type!r}")
         self.audio_preprocess_type = audio_preprocess_type
         self.honk_graph = honk_graph
         self.honk_latency = honk_latency
+        self.honk_decide = honk_decide
         self.labels = labels
         self.model_filename = model_filename
         self.no_cuda = no_cuda
@@ -143,13 +156,79 @@ class TorchLabelService(LabelService):
             predictions = F.softmax(self._forward1(model_in).squeeze(0).cpu(), dim=0).numpy()
         return (self.labels[np.argmax(predictions)], np.max(predictions))
 
+    def decide(self, logits, window0=None, keyword=None, min_keyword_prob=0.85):
+        """The stage after the forward, on logits [N, n_labels] -> numpy ``(label int32 [N], prob float32
+        [N])``: what softmax -> np.argmax / np.max give per row (the first index of the largest logit and
+        its probability; a row whose softmax is NaN -- a NaN, a +inf, nothing above -inf -- gives label 0,
+        prob NaN).  With ``window0`` (int64 [S + 1], starting at 0, non-decreasing, ending at N: the layout
+        ``compute_*_segments`` and ``StreamBank.tick`` return) also ``(sums float64 [S, n_labels], counts
+        int32 [S, n_labels], hit int64 [S])`` over segment s = rows ``window0[s]:window0[s + 1]``: the summed
+        prob and the number of its rows per label, and the segment-relative index of the first row labelled
+        ``keyword`` (a label's name or index; None: no keyword) with ``prob >= min_keyword_prob``, else -1.
+        A finite prob is a multiple of 2^-29 within [2^-6, 1] up to 64 labels, so the sums are exact in
+        double whatever the order they are taken in.
+
+        A ROCm tensor of at most 64 labels: one honk_listen_decide_f32 (csrc/listen.hip) and ONE download, of
+        these small arrays (not of the logits).  Otherwise (a CPU tensor, more labels): the same definition
+        with torch's softmax and numpy."""
+        from . import _native
+        if logits.dim() != 2:
+            raise ValueError("decide: logits must be [N, n_labels]")
+        n, n_labels = logits.shape
+        if keyword is None:
+            kw = -1
+        elif isinstance(keyword, str):
+            kw = self.labels.index(keyword) if keyword in self.labels else -1
+        else:
+            kw = int(keyword)
+        w0 = None if window0 is None else _native.listen_window0(window0, n, "decide")
+        if (logits.is_cuda and logits.dtype == torch.float32 and 1 <= n_labels <= _native.LISTEN_MAX_LABELS
+                and n <= _native.LISTEN_MAX_WINDOWS):
+            parts = _native.listen_decide(logits, w0, kw, min_keyword_prob)
+            # one download: the 8-byte arrays first, so every view below is aligned
+            order = [parts[i] for i in ((2, 4, 0, 1, 3) if w0 is not None else (0, 1))]
+            raw = torch.cat([t.reshape(-1).view(torch.uint8) for t in order]).cpu().numpy()
+            got, at = [], 0
+            for t in order:
+                nb = t.numel() * t.element_size()
+                got.append(raw[at:at + nb].view(_NUMPY_OF[t.dtype]).reshape(tuple(t.shape)))
+                at += nb
+            if w0 is None:
+                return got[0], got[1]
+            return got[2], got[3], got[0], got[4], got[1]
+        with torch.no_grad():
+            p = F.softmax(logits.detach().cpu().float(), dim=1).numpy()
+        label = np.argmax(p, axis=1).astype(np.int32) if n else np.zeros(0, np.int32)
+        prob = np.max(p, axis=1) if n else np.zeros(0, np.float32)
+        if w0 is None:
+            return label, prob
+        segments = w0.size - 1
+        seg = np.repeat(np.arange(segments), np.diff(w0))
+        p64 = prob.astype(np.float64)
+        sums = np.zeros((segments, n_labels), np.float64)
+        counts = np.zeros((segments, n_labels), np.int32)
+        np.add.at(sums, (seg, label), p64)   # in row order: the host loop's sums
+        np.add.at(counts, (seg, label), 1)
+        first = np.full(segments, n, np.int64)
+        rows = np.flatnonzero((label == kw) & (p64 >= min_keyword_prob)) if kw >= 0 else np.zeros(0, np.int64)
+        np.minimum.at(first, seg[rows], rows - w0[seg[rows]])
+        return label, prob, sums, counts, np.where(first == n, -1, first)
+
+    def _labelled(self, logits):
+        """[(label, prob)] of the rows of ``logits``: the logits downloaded, softmax and argmax / max row by
+        row on the host -- or, under ``honk_decide``, both from ``decide``."""
+        if self.honk_decide:
+            label, prob = self.decide(logits)
+            return list(zip(np.asarray(self.labels, dtype=object)[label].tolist(), prob.astype(np.float64).tolist()))
+        p = F.softmax(logits.cpu(), dim=1).numpy()
+        return [(self.labels[int(np.argmax(r))], float(np.max(r))) for r in p]
+
     def label_batch(self, windows):
         """All windows of a request in ONE MFCC launch + ONE forward; [(label, prob)] in order."""
         if not windows:
             return []
         with torch.no_grad():
-            p = F.softmax(self._net()(self._model_input(windows)).cpu(), dim=1).numpy()
-        return [(self.labels[int(np.argmax(r))], float(np.max(r))) for r in p]
+            return self._labelled(self._net()(self._model_input(windows)))
 
     def listen(self, wav_data, stride_size_ms=500, method="labels", keyword="command", min_keyword_prob=0.85):
         """Batched form of server.py:99-112 (ListenEndpoint.POST): 1 s windows every
@@ -172,30 +251,43 @@ class TorchLabelService(LabelService):
         bounded whatever the recording's length.  Under PCEN the windows go through
         ``compute_pcen_windows``: the mel energies of each STFT frame once, then every window its own
         smoother; no float copy of the windows is built."""
+        stride_bytes = self._stride_bytes("label_stream", stride_size_ms, max_windows)
+        out = []
+        for logits in self._recording_logits(wav_data, stride_bytes, max_windows):
+            out.extend(self._labelled(logits))
+        return out
+
+    def _stride_bytes(self, who, stride_size_ms, max_windows):
         stride_bytes = int(2 * 16000 * stride_size_ms / 1000)
         if stride_bytes < 1:
-            raise ValueError("label_stream: stride_size_ms too small")
+            raise ValueError(f"{who}: stride_size_ms too small")
+        if max_windows < 1 and not (self.no_cuda or stride_bytes % 2):
+            raise ValueError(f"{who}: max_windows >= 1")
+        return stride_bytes
+
+    def _recording_logits(self, wav_data, stride_bytes, max_windows):
+        """The logits of one recording's windows, in order, in pieces: on the CPU (or with an odd stride in
+        bytes) one piece, ``label_batch``'s forward of ``stride(...)``; else ``label_stream``'s pieces of at
+        most ``max_windows`` windows off the recording uploaded once."""
         if self.no_cuda or stride_bytes % 2:
-            return self.label_batch(list(stride(wav_data, stride_bytes, 2 * 16000)))
-        if max_windows < 1:
-            raise ValueError("label_stream: max_windows >= 1")
+            windows = list(stride(wav_data, stride_bytes, 2 * 16000))
+            if windows:
+                with torch.no_grad():
+                    logits = self._net()(self._model_input(windows))
+                yield logits
+            return
         n = len(wav_data) // 2
         total = 0 if n < 16000 else 1 + (n - 16000) // (stride_bytes // 2)
         if total == 0:
-            return []
+            return
         device = next(self.model.parameters()).device
         pcm = torch.from_numpy(np.frombuffer(wav_data, dtype=np.int16, count=n).copy()).to(device)
-        out = []
-        with torch.no_grad():
-            for w0 in range(0, total, max_windows):
-                nw = min(max_windows, total - w0)
-                if self.audio_preprocess_type == "PCEN":
-                    x = self.audio_processor.compute_pcen_windows(pcm, stride_bytes // 2, 16000, w0, nw)
-                else:
-                    x = self.audio_processor.compute_mfccs_windows(pcm, stride_bytes // 2, 16000, w0, nw)
-                p = F.softmax(self._net()(x).cpu(), dim=1).numpy()
-                out.extend((self.labels[int(np.argmax(r))], float(np.max(r))) for r in p)
-        return out
+        windows = self.audio_processor.compute_pcen_windows if self.audio_preprocess_type == "PCEN" else \
+            self.audio_processor.compute_mfccs_windows
+        for w0 in range(0, total, max_windows):
+            with torch.no_grad():
+                logits = self._net()(windows(pcm, stride_bytes // 2, 16000, w0, min(max_windows, total - w0)))
+            yield logits
 
     def label_streams(self, recordings, stride_size_ms=500, max_windows=8192):
         """``[label_stream(r, stride_size_ms) for r in recordings]`` (int16 byte strings) with the whole
@@ -204,43 +296,73 @@ class TorchLabelService(LabelService):
         (``compute_pcen_segments`` under PCEN), one forward, one softmax and one download per batch.  A
         recording with more than ``max_windows`` windows goes through ``label_stream`` itself.  On the
         CPU, or with an odd stride in bytes, it is ``label_stream`` per recording."""
-        stride_bytes = int(2 * 16000 * stride_size_ms / 1000)
-        if stride_bytes < 1:
-            raise ValueError("label_streams: stride_size_ms too small")
-        if self.no_cuda or stride_bytes % 2:
-            return [self.label_stream(r, stride_size_ms, max_windows) for r in recordings]
-        if max_windows < 1:
-            raise ValueError("label_streams: max_windows >= 1")
-        step = stride_bytes // 2
-        ns = [len(r) // 2 for r in recordings]
-        Ws = [0 if n < 16000 else 1 + (n - 16000) // step for n in ns]
+        stride_bytes = self._stride_bytes("label_streams", stride_size_ms, max_windows)
         out = [[] for _ in recordings]
+        for recs, logits, w0 in self._streams_logits(recordings, stride_bytes, max_windows):
+            got = self._labelled(logits)
+            for j, i in enumerate(recs):
+                out[i] += got[w0[j]:w0[j + 1]]
+        return out
+
+    def _streams_logits(self, recordings, stride_bytes, max_windows):
+        """``label_streams``' batching -> (recs, logits, window0) per forward: the logits of the windows of
+        recordings ``recs`` (indices), recording ``recs[j]``'s rows ``window0[j]:window0[j + 1]``.  A
+        recording's windows come in order; one with more than ``max_windows`` windows -- and, on the CPU or
+        with an odd stride in bytes, every recording -- comes alone, in ``_recording_logits``' pieces."""
+        alone = range(len(recordings))
+        if not (self.no_cuda or stride_bytes % 2):
+            step = stride_bytes // 2
+            ns = [len(r) // 2 for r in recordings]
+            Ws = [0 if n < 16000 else 1 + (n - 16000) // step for n in ns]
+            alone = [i for i, w in enumerate(Ws) if w > max_windows]
+        for i in alone:
+            for logits in self._recording_logits(recordings[i], stride_bytes, max_windows):
+                yield [i], logits, np.array([0, logits.shape[0]], np.int64)
+        if self.no_cuda or stride_bytes % 2:
+            return
         batched = [i for i, w in enumerate(Ws) if 0 < w <= max_windows]
-        for i, w in enumerate(Ws):
-            if w > max_windows:
-                out[i] = self.label_stream(recordings[i], stride_size_ms, max_windows)
         if not batched:
-            return out
+            return
         device = next(self.model.parameters()).device
         off = np.concatenate([[0], np.cumsum([ns[i] for i in batched])]).astype(np.int64)
         pcm = torch.from_numpy(np.concatenate([np.frombuffer(recordings[i], dtype=np.int16, count=ns[i])
                                                for i in batched])).to(device)
         segments = self.audio_processor.compute_pcen_segments if self.audio_preprocess_type == "PCEN" else \
             self.audio_processor.compute_mfccs_segments
-        with torch.no_grad():
-            a = 0
-            while a < len(batched):
-                b, nw = a, 0
-                while b < len(batched) and nw + Ws[batched[b]] <= max_windows:
-                    nw += Ws[batched[b]]
-                    b += 1
+        a = 0
+        while a < len(batched):
+            b, nw = a, 0
+            while b < len(batched) and nw + Ws[batched[b]] <= max_windows:
+                nw += Ws[batched[b]]
+                b += 1
+            with torch.no_grad():
                 x, w0 = segments(pcm, off[a:b + 1], step, 16000)
-                p = F.softmax(self._net()(x).cpu(), dim=1).numpy()
-                for j in range(a, b):
-                    out[batched[j]] = [(self.labels[int(np.argmax(r))], float(np.max(r)))
-                                       for r in p[w0[j - a]:w0[j - a + 1]]]
-                a = b
-        return out
+                logits = self._net()(x)
+            yield batched[a:b], logits, w0
+            a = b
+
+    def listen_streams(self, recordings, stride_size_ms=500, method="labels", keyword="command",
+                       min_keyword_prob=0.85, max_windows=8192):
+        """``[listen_stream(r, stride_size_ms, method, keyword, min_keyword_prob) for r in recordings]`` off
+        ``label_streams``' batching -- one front-end call and one forward per batch of at most ``max_windows``
+        windows -- with ``decide`` on each batch's ``window0``: every recording's answer is made from its
+        ``sums`` / ``counts`` / ``hit`` (a label is a key where its count is non-zero; the early exit of
+        "command_tagging" is ``hit >= 0``), no (label, prob) list is built."""
+        stride_bytes = self._stride_bytes("listen_streams", stride_size_ms, max_windows)
+        n_rec, n_labels = len(recordings), len(self.labels)
+        sums, counts = np.zeros((n_rec, n_labels)), np.zeros((n_rec, n_labels), np.int64)
+        hit, seen = np.full(n_rec, -1, np.int64), np.zeros(n_rec, np.int64)
+        for recs, logits, w0 in self._streams_logits(recordings, stride_bytes, max_windows):
+            _, _, s, c, h = self.decide(logits, w0, keyword, min_keyword_prob)
+            recs = np.asarray(recs)
+            found = (hit[recs] < 0) & (h >= 0)
+            hit[recs[found]] = seen[recs[found]] + h[found]
+            sums[recs] += s       # (exact: a recording's pieces add up to the sum of its windows' probs)
+            counts[recs] += c
+            seen[recs] += np.diff(w0)
+        if method == "command_tagging":
+            return [dict(contains_command=bool(h >= 0)) for h in hit]
+        return [{self.labels[l]: float(sums[i, l]) for l in np.flatnonzero(counts[i])} for i in range(n_rec)]
 
     def listen_stream(self, wav_data, stride_size_ms=500, method="labels", keyword="command", min_keyword_prob=0.85):
         """``listen`` over ``label_stream``: the same return contract and early-exit order."""
@@ -308,7 +430,8 @@ class StreamPool(object):
     windows, one softmax and one download.  A chunk that ends mid-sample leaves its odd byte on the host, in
     front of that key's next chunk.  Where the bank cannot be built (a CPU service, an odd stride in bytes,
     a shape its plan or its tick refuses: ``stream_bank`` raises ValueError for both at construction) the
-    pool warns once and works as with ``device_state=False``."""
+    pool warns once and works as with ``device_state=False``.  ``feed_arrays`` is a bank tick fed and read
+    as arrays: one int16 array in, ``(label, prob, window0)`` out."""
 
     MAX_WINDOWS = 8192
 
@@ -380,13 +503,42 @@ class StreamPool(object):
         off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
         x, w0 = self.bank.tick(ids, torch.from_numpy(np.concatenate(parts)), off)
         if x.shape[0]:
-            with torch.no_grad():
-                net = svc._net()
-                logits = torch.cat([net(x[a:a + self.MAX_WINDOWS]) for a in range(0, x.shape[0], self.MAX_WINDOWS)])
-                p = F.softmax(logits.cpu(), dim=1).numpy()
+            got = svc._labelled(self._forward(x))
             for j, key in enumerate(chunks):
-                out[key] = [(svc.labels[int(np.argmax(r))], float(np.max(r))) for r in p[w0[j]:w0[j + 1]]]
+                out[key] = got[w0[j]:w0[j + 1]]
         return out
+
+    def _forward(self, x):
+        """The logits of a tick's windows: the forward in slices of at most MAX_WINDOWS."""
+        with torch.no_grad():
+            net = self.service._net()
+            return torch.cat([net(x[a:a + self.MAX_WINDOWS]) for a in range(0, x.shape[0], self.MAX_WINDOWS)])
+
+    def feed_arrays(self, keys, pcm, offsets):
+        """``feed`` as arrays, for a pool on a bank (``device_state=True``; ValueError otherwise): ``pcm`` is
+        one int16 numpy array or tensor holding the new samples of ``keys`` (distinct), key r's being
+        ``pcm[offsets[r]:offsets[r + 1]]`` -> numpy ``(label int32 [N], prob float32 [N], window0 int64
+        [len(keys) + 1])``: the windows key r completes are rows ``window0[r]:window0[r + 1]``, their label an
+        index into the service's labels.  One bank tick, the forward in slices of at most MAX_WINDOWS, one
+        ``decide``; apart from the key -> slot lookup nothing is done per stream.  A key is opened at its
+        first feed, and may be fed through ``feed`` on another tick (whose odd-byte carry is ``feed``'s alone:
+        whole samples come in here)."""
+        if self.bank is None:
+            raise ValueError("StreamPool.feed_arrays: the pool has no stream bank (device_state=True on a ROCm "
+                             "service with an even stride in bytes)")
+        if not torch.is_tensor(pcm):
+            pcm = torch.from_numpy(np.ascontiguousarray(pcm))
+        ids = []
+        for key in keys:
+            st = self._streams.get(key)
+            if st is None:
+                st = self._streams[key] = [self.bank.open(), b""]
+            ids.append(st[0])
+        x, w0 = self.bank.tick(ids, pcm, offsets)
+        if not x.shape[0]:
+            return np.zeros(0, np.int32), np.zeros(0, np.float32), w0
+        label, prob = self.service.decide(self._forward(x))
+        return label, prob, w0
 
 
 def stride(array, stride_size, window_size):

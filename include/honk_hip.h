@@ -766,6 +766,52 @@ int honk_pcen_bank_tick_i16(const int16_t* chunks_dev, const honk_bank_slot_t* s
                             float* out /* [windows][1 + window/hop][n_mels] */,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * The last stage of /listen (ListenEndpoint.POST over TorchLabelService.label:
+ * softmax -> np.argmax / np.max per window, then {label: summed prob} or the
+ * command_tagging early exit per recording), on logits [n][n_labels] that stay on the
+ * device.  Every pointer is device memory; the call only enqueues (rows, then segments:
+ * two launches), needs no workspace and can be captured in a graph.
+ *
+ * Per window w:
+ *   label[w] = the first index of the largest logit;
+ *   prob[w]  = 1 / sum_j expf(z_j - max z) in fp32, summed in ascending j
+ * -- independent of n and of the other windows, bit-equal from run to run.  A row whose
+ * softmax is NaN in IEEE arithmetic (any NaN, any +inf, nothing above -inf) gives label 0,
+ * prob NaN: what np.argmax / np.max return on torch's all-NaN softmax row.  A -inf among
+ * finite logits is an ordinary zero term.
+ *
+ * Per segment s = windows [window0[s], window0[s+1]) (the layout of the segments calls'
+ * and the bank ticks' window0, copied to the device by the caller):
+ *   counts[s][l] = the number of its windows labelled l;
+ *   sums[s][l]   = the sum of their prob in double;
+ *   hit[s]       = the segment-relative index of the first window with label == keyword
+ *                  && (double)prob >= min_prob, else -1 (always -1 for keyword < 0; NaN
+ *                  compares false).
+ * An empty segment gets zeros and -1.  A finite prob is at least 1 / n_labels >= 2^-6, hence
+ * a multiple of 2^-29, and a sum of up to 2^23 of them is exact in double: sums does not
+ * depend on the order of summation and equals the sequential host loop bit for bit (a NaN
+ * prob makes its label's -- label 0's -- sum NaN).  A table entry is clamped to [0, n]
+ * before use, so no table makes the call read outside label / prob; the results for a table
+ * that decreases are unspecified.
+ * segments == 0: window0_dev / sums / counts / hit may be NULL and are not touched.
+ * n == 0: nothing per window is written (logits / label / prob may be NULL).
+ * Status, decided on the host before anything is enqueued (honk_last_error has the text):
+ * HONK_ERR_ARG (a negative count, a null pointer the counts require); HONK_ERR_UNSUPPORTED
+ * (n_labels outside [1, HONK_LISTEN_MAX_LABELS], n above HONK_LISTEN_MAX_WINDOWS).
+ * No float atomics; within a launch no location is written by one workgroup and read by
+ * another.  Memory contract: label / prob [n], sums / counts [segments][n_labels] and hit
+ * [segments] are fully written and nothing outside them; logits and window0_dev are never
+ * modified.
+ */
+#define HONK_LISTEN_MAX_LABELS 64
+#define HONK_LISTEN_MAX_WINDOWS ((int64_t)1 << 23)
+int honk_listen_decide_f32(const float* logits, int64_t n, int32_t n_labels, const int64_t* window0_dev,
+                           int64_t segments, int32_t keyword, double min_prob,
+                           int32_t* label, float* prob /* [n] */,
+                           double* sums, int32_t* counts /* [segments][n_labels] */,
+                           int64_t* hit /* [segments] */, void* stream);
+
 /* ---- training (data-parallel train(), utils/train.py:99-135) -------------------- */
 /*
  * One torch.optim.SGD step (dampening 0) over a flat fp32 parameter bucket whose
