@@ -1178,7 +1178,9 @@ __global__ __launch_bounds__(256) void pack_range_kernel(float* __restrict__ rec
 // The clip's power-of-two scale (see above): one wave per clip; a clip with a
 // non-finite input keeps s_model (its NaN / Inf propagates as in the reference).
 // flags (may be null): [n] the clips' admission flags, initialised here (2: the input is
-// not finite, else 0; tail_sum_kernel raises 1).
+// not finite; 1: the scale lies more than HONK_F16X2_DROP_MAX binades below s_model -- a
+// clip with an entry that loud against the model's range is re-run whatever its last-layer
+// means say, see honk_hip.h; else 0; tail_sum_kernel raises 1).
 __global__ __launch_bounds__(256) void clip_scale_kernel(const float* __restrict__ x, const float* __restrict__ rec,
                                                          float* __restrict__ cscale, int n, int hw,
                                                          int* __restrict__ flags) {
@@ -1211,16 +1213,17 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(const float* __restrict
   bad = __any(bad);
   float s = rec[HONK_NUM_SCALE];
   const float M = rec[HONK_NUM_RANGE], bound = mx * rec[HONK_NUM_W0SUM];
+  int ex = 0;
   if (!bad && M > 0.f && bound > M) {
     const float r = bound / M;
-    int ex = 126;
+    ex = 126;
     if (r <= 1e37f) (void)frexpf(r, &ex);  // r < 2^ex
     s = ldexpf(s, -ex);
   }
   s = fminf(fmaxf(s, 0x1p-24f), 0x1p14f);  // channel C holds s: an exact fp16 value
   if (lane == 0) {
     cscale[clip] = s;
-    if (flags) flags[clip] = bad ? 2 : 0;
+    if (flags) flags[clip] = bad ? 2 : ex > HONK_F16X2_DROP_MAX ? 1 : 0;
   }
 }
 
@@ -2694,11 +2697,11 @@ static int rerun_flagged(const Layout& L, const honk_res_desc* d, const Switches
 static int res_forward(const honk_res_desc* d, const float* packed, const float* x, float* logits, int64_t batch,
                        void* workspace, size_t ws_bytes, void* stream, bool ordered, int64_t cap,
                        int32_t* flagged_out, bool latency = false) {
+  g_rerun = 0;  // (before every return: an empty or refused call re-ran nothing)
   Layout L;
   int rc = make_layout(d, &L);
   if (rc) return rc;
   if (batch < 0) return fail(HONK_ERR_ARG, "negative batch");
-  if (ordered) g_rerun = 0;
   if (batch == 0) {
     if (ordered && flagged_out) {
       hipLaunchKernelGGL(count_out_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const int*)nullptr,
@@ -2722,7 +2725,6 @@ static int res_forward(const honk_res_desc* d, const float* packed, const float*
   hipStream_t st = (hipStream_t)stream;
   const int64_t chunk = chunk_clips(L, sw, batch);
   const bool admission = L.prec == HONK_PREC_F16X2 && sw.rerun_on();
-  g_rerun = 0;
   if (ordered && flagged_out && !admission) {
     hipLaunchKernelGGL(count_out_kernel, dim3(1), dim3(1), 0, st, (const int*)nullptr, flagged_out);
     HONK_LAUNCH_CHECK("res count_out_kernel");

@@ -438,6 +438,8 @@ class SpeechResModel(SerializableModule):
                 self.honk_last_rerun = None
                 self.honk_last_rerun_dev = torch.zeros((), dtype=torch.int32, device=x.device)
             if B == 0:
+                if not ordered:
+                    self.honk_last_rerun = 0  # (not the previous batch's count)
                 return out
             ws_query = "honk_res_latency_workspace_bytes" if latency else "honk_res_workspace_bytes"
             ws_bytes = getattr(lib, ws_query)(desc, B)

@@ -180,8 +180,9 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
  * f16x2 pass, a clip whose last-layer BatchNorm'd channel means lie beyond
  * HONK_F16X2_Z_MAX standard deviations of the model's calibration (an input far outside
  * the distribution the running statistics describe: f16x2's rounding is no longer
- * averaged away there), or whose f16x2 logits are not finite while its input is, is
- * re-run in BF16X3 and its logits replaced.  This is the one honk_res_forward mode that
+ * averaged away there), or whose f16x2 logits are not finite while its input is, or whose
+ * scale was lowered by more than HONK_F16X2_DROP_MAX binades (below), is re-run in BF16X3
+ * and its logits replaced.  This is the one honk_res_forward mode that
  * SYNCHRONISES `stream` (once per call, to read the flagged-clip count; not capturable
  * in a hipGraph -- honk_res_forward_ordered below is).  HONK_F16X2_RERUN=0 in the
  * environment turns the admission off (raw f16x2: kernel tests).  The workspace
@@ -190,6 +191,16 @@ int honk_res_select_precision(const honk_res_desc* d, const float* rec, int32_t 
 int honk_res_forward(const honk_res_desc* d, const float* packed, const float* x, float* logits,
                      int64_t batch, void* workspace, size_t workspace_bytes, void* stream);
 #define HONK_F16X2_Z_MAX 8
+/* The second admission statistic, the clip's crest against the model: a clip's scale is
+   s_model lowered by ex binades, max|x| * HONK_NUM_W0SUM / HONK_NUM_RANGE < 2^ex
+   (HONK_NUM_SCALE above).  One loud entry or frame in an otherwise calibrated clip (a click)
+   lowers the scale but barely moves a last-layer channel mean, an average over the whole
+   map, while the fp16 rounding of the large values around it is absolute in size: measured
+   on tests/golden/range_res15-spike.npz, clips at ex <= 4 stay within half the 1e-4 bar,
+   clips at ex = 6 reach 1.6 bars with |z| <= 7.  A clip with ex > HONK_F16X2_DROP_MAX is
+   flagged by the scale pass itself (no cost on the forward path); calibrated inputs sit at
+   ex <= 3 (the round-6 admission). */
+#define HONK_F16X2_DROP_MAX 4
 /* The clips the calling thread's last honk_res_forward re-ran in bf16x3 (0 unless F16X2;
    0 after honk_res_forward_ordered: the host does not learn the count). */
 int64_t honk_res_rerun_count(void);

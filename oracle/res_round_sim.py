@@ -13,6 +13,9 @@ The inference kernels' arithmetic in float64 except for the operand roundings, p
   * "f16s": as f16c, but the stored value is x - mean_BN (the conv input after the
             BN shift, so zero padding needs no border bias)
   * "f16w1": input stored as one fp16; weights as ONE fp16 (RNE); one product hw*x
+An "f16" tensor may carry a per-clip power-of-two scale s (clip_scale_kernel's: s_model
+lowered by the binades the clip's conv0 bound exceeds the model's range): it is stored as
+f16(t * s) / s, so a loud clip's small values meet fp16's subnormals as on the device.
 The border-class bias (folded BN) is exact.  The conv0 output (layer 0) and every
 layer output are stored in the format of the layer that reads them as input.
 Accumulation, the spatial mean and the head are exact, so a simulated error is the share
@@ -43,9 +46,17 @@ def conv(x, w, d):
     return orc.conv2d(x, w, padding=(d, d), dilation=(d, d))
 
 
-def layer_conv(x, W, mean, var, d, scheme):
+def f16_scaled(x, scale):
+    """One fp16 at the clips' scales: f16(x * s) / s, s [B] (None: s = 1)."""
+    if scale is None:
+        return f16(x)
+    s = np.asarray(scale, np.float64).reshape(-1, 1, 1, 1)
+    return f16(np.asarray(x, np.float64) * s) / s
+
+
+def layer_conv(x, W, mean, var, d, scheme, scale=None):
     """conv(bn(x)) with zero padding of the post-BN tensor, x the stored pre-BN tensor
-    (already rounded to its storage), in the scheme's products."""
+    (already rounded to its storage), in the scheme's products.  scale: "f16" only."""
     s = 1.0 / np.sqrt(var.astype(np.float64) + 1e-5)
     Ws = W.astype(np.float64) * s[None, :, None, None]
     valid = np.ones_like(x[:1, :1])
@@ -58,7 +69,7 @@ def layer_conv(x, W, mean, var, d, scheme):
         return conv(hx + lx, hw, d) + conv(hx, lw, d) - bias
     if scheme in ("f16", "f16c"):
         hw, lw = split(Ws, f16)
-        xc = f16(x)          # the conv reads one fp16 (f16c: the hi half)
+        xc = f16_scaled(x, scale if scheme == "f16" else None)  # the conv reads one fp16 (f16c: the hi half)
         return conv(xc, hw + lw, d) - bias
     if scheme == "f16w1":
         return conv(f16(x), f16(Ws), d) - bias
@@ -71,14 +82,17 @@ def layer_conv(x, W, mean, var, d, scheme):
     raise ValueError(scheme)
 
 
-def store(x, scheme):
-    """The stored tensor's value as the residual add sees it."""
+def store(x, scheme, scale=None):
+    """The stored tensor's value as the residual add sees it.  scale: the clips' scales
+    ([B], "f16" only)."""
     if scheme == "exact":
         return x
     if scheme == "x3":
         h, l = split(x, bf16)
         return h + l
-    if scheme in ("f16", "f16w1"):
+    if scheme == "f16":
+        return f16_scaled(x, scale)
+    if scheme == "f16w1":
         return f16(x)
     if scheme == "bf16":
         return bf16(x)
@@ -88,9 +102,21 @@ def store(x, scheme):
     raise ValueError(scheme)
 
 
-def fwd(params, cfg, x, schemes):
+def clip_scales(x, s_model, M, w0sum):
+    """clip_scale_kernel (honk_amd/csrc/res.hip) restated: per clip (scale, binades below
+    s_model).  bound = max|x| * w0sum; where it exceeds M the scale drops by the exponent
+    ex of bound / M (bound / M < 2^ex), and is clamped to [2^-24, 2^14]."""
+    mx = np.abs(np.asarray(x, np.float32)).reshape(len(x), -1).max(axis=1)
+    bound = mx * np.float32(w0sum)
+    r = (bound / np.float32(M)).astype(np.float32)
+    ex = np.where(bound > np.float32(M), np.frexp(r)[1], 0).astype(np.int64)
+    s = np.clip(np.ldexp(np.float64(s_model), -ex), 2.0 ** -24, 2.0 ** 14)
+    return s, ex
+
+
+def fwd(params, cfg, x, schemes, scale=None):
     """schemes[i] = format of the tensor layer i (1..L) reads (i.e. layer i-1's output).
-    x: [B, H, W], any H and W the model takes."""
+    x: [B, H, W], any H and W the model takes.  scale: [B] the clips' scales of "f16" stores."""
     x = np.asarray(x, np.float64)[:, None]
     L = int(cfg["n_layers"])
     y = orc.relu(orc.conv2d(x, params["conv0.weight"], padding=(1, 1)))
@@ -100,7 +126,7 @@ def fwd(params, cfg, x, schemes):
     old = y
     for i in range(1, L + 1):
         sc = schemes[i]
-        xin = store(cur, sc)
+        xin = store(cur, sc, scale)
         if i % 2 == 1:
             # cur is a residual-stream tensor (conv0 output or an even layer's sum):
             # the residual of layer i+1 reads the stored value
@@ -108,7 +134,7 @@ def fwd(params, cfg, x, schemes):
         d = orc.res_dilation(cfg, i)
         mean = params[f"bn{i - 1}.running_mean"] if i > 1 else np.zeros(xin.shape[1], np.float32)
         var = params[f"bn{i - 1}.running_var"] if i > 1 else np.full(xin.shape[1], 1.0 - 1e-5, np.float32)
-        h = orc.relu(layer_conv(xin, params[f"conv{i}.weight"], mean, var, d, sc))
+        h = orc.relu(layer_conv(xin, params[f"conv{i}.weight"], mean, var, d, sc, scale))
         cur = h + old if i % 2 == 0 else h
     z = orc.batch_norm_eval(cur, params[f"bn{L}.running_mean"], params[f"bn{L}.running_var"])
     z = z.reshape(z.shape[0], z.shape[1], -1).mean(axis=2)

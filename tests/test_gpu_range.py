@@ -117,7 +117,7 @@ def test_f16x2_out_of_distribution_stays_finite(monkeypatch):
     assert (out["f16x2"].argmax(1) == logits.argmax(1)).all()
 
 
-@pytest.mark.parametrize("name", ["res15-k2000", "res15-ood", "res8-k2000", "res15-speech"])
+@pytest.mark.parametrize("name", ["res15-k2000", "res15-ood", "res8-k2000", "res15-speech", "res15-spike"])
 def test_numerics_record_matches_restatement(name):
     cfg, params, x, logits, model = load_range_fixture(name)
     m = module(cfg, params, model)
@@ -259,3 +259,133 @@ def test_admission_flags_only_out_of_calibration_clips():
         out = m(x)
         assert m.honk_last_rerun == 0
         assert torch.isnan(out[3]).all() and torch.isfinite(out[torch.arange(256) != 3]).all()
+
+
+def test_empty_batch_reports_no_rerun():
+    """honk_res_rerun_count() after an empty batch is 0, not the previous call's count: a
+    flagged batch through the C ABI, then batch == 0 (and the module's honk_last_rerun)."""
+    import ctypes
+    lib = _native.load()
+    cfg, params, x, logits, meta = load_fixture("res15-b3-mfcc")
+    _, _, x_ood, _, _ = load_range_fixture("res15-ood")
+    m = module(cfg, params, "res15", "f16x2")
+    m.honk_reroute = False
+    xd = torch.as_tensor(x_ood).to(DEV)
+    desc, packed, B = m._desc(101, 40, "f16x2"), m._packed(xd), len(x_ood)
+    ws_bytes = lib.honk_res_workspace_bytes(desc, B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
+    out = torch.empty(B, 12, device=DEV)
+    stream = _native.stream_handle(xd.device)
+
+    def forward(batch):
+        _native.check(lib.honk_res_forward(ctypes.byref(desc), packed.data_ptr(), xd.data_ptr(), out.data_ptr(), batch,
+                                           ws.data_ptr(), ws_bytes, stream), "honk_res_forward")
+        return int(lib.honk_res_rerun_count())
+
+    assert forward(B) == B
+    assert forward(0) == 0
+    run(m, x_ood)
+    assert m.honk_last_rerun == B
+    empty = run(m, x_ood[:0])
+    assert empty.shape == (0, 12) and m.honk_last_rerun == 0
+
+
+# ---- range_res15-spike: one loud entry / frame in a speech-scale clip ----------------------
+class Spike:
+    pass
+
+
+@pytest.fixture(scope="module")
+def spike(_need_gpu):
+    """The spike batch under auto latched on f16x2 (the clean res15-speech batch first: the
+    policy's probe must not see the spiked clips and pick bf16x3 for the whole model), the raw
+    f16x2 logits (HONK_F16X2_RERUN=0) and the CPU test's classes -- computed once."""
+    from test_range import spike_fixture
+    s = Spike()
+    s.f = f = spike_fixture()
+    with pytest.MonkeyPatch.context() as mp:
+        for v in ("HONK_PRECISION", "HONK_RES_KERNEL", "HONK_LAST_KERNEL", "HONK_CONV0", "HONK_F16X2_RERUN",
+                  "HONK_RES_CHUNK"):
+            mp.delenv(v, raising=False)
+        _, p_speech, x_speech, l_speech, _ = load_range_fixture("res15-speech")
+        assert all(np.array_equal(f["params"][k], p_speech[k]) for k in p_speech)  # the same model
+        s.m = module(f["cfg"], f["params"], f["model"])
+        out = run(s.m, x_speech)
+        assert s.m.honk_last_precision == "f16x2" and s.m.honk_last_rerun == 0
+        np.testing.assert_allclose(out, l_speech, atol=ATOL, rtol=0)
+        s.clean = out
+        s.out = run(s.m, f["x"])
+        s.precision, s.rerun = s.m.honk_last_precision, s.m.honk_last_rerun
+        mp.setenv("HONK_F16X2_RERUN", "0")
+        s.raw = run(s.m, f["x"])
+        assert s.m.honk_last_rerun == 0
+    s.bar = ATOL * np.maximum(1.0, np.abs(f["logits"]).max(axis=1))
+    s.err = np.abs(s.out - f["logits"]).max(axis=1)
+    s.raw_err = np.abs(s.raw - f["logits"]).max(axis=1)
+    s.reran = ~(s.out == s.raw).all(axis=1)   # a re-run replaced the clip's f16x2 logits
+    return s
+
+
+def _spike_table(s, err, what):
+    f = s.f
+    for i in range(len(err)):
+        print(f"clip {i:2d} kind {f['kind'][i]} amp {f['amp'][i]:8.0f} frame {f['frame'][i]:3d} scale 2^-{f['ex'][i]:<2d} "
+              f"max|z| {f['zmax'][i]:8.2f} re-run {int(s.reran[i])}: {what} err {err[i]:.2e} = {err[i] / s.bar[i]:5.2f} bar")
+
+
+def test_spike_clips_hold_the_bar_or_are_rerun(spike):
+    """a loud entry in a speech-scale clip.  Every clip of the batch is
+    within 1e-4 max(1, max|reference logit of the clip|) of the reference's logits under auto
+    = f16x2; the clips re-run in bf16x3 are exactly those the CPU test computes (|z| > 8 from
+    the float64 oracle, or a scale more than HONK_F16X2_DROP_MAX binades below s_model), and
+    they are within the probe's bar.
+
+    Measured (MI355X), err / bar: the 7 clips left to f16x2 <= 0.48 (clean 0.10, c0 -300 0.20,
+    -500 and -650 0.45, x[20, 39] = 300 0.37, a +-30 frame 0.48); the 17 re-run clips
+    <= 0.07.  Without the scale-drop flag (the |z| statistic alone re-ran 10 clips): c0 = -2500
+    at frame 50 sat at 1.56 and 1.08 bars with max|z| 6.9 / 7.65, not re-run."""
+    s, f = spike, spike.f
+    _spike_table(s, s.err, "auto")
+    assert s.precision == "f16x2"
+    assert np.isfinite(s.out).all()
+    assert (s.err <= s.bar).all(), np.nonzero(s.err > s.bar)[0]
+    assert np.array_equal(s.reran, f["rerun"]), (np.nonzero(s.reran)[0], np.nonzero(f["rerun"])[0])
+    assert s.rerun == int(f["rerun"].sum())
+    assert (np.abs(s.out - f["logits"]) <= _rel_bound(f["logits"]))[s.reran].all()
+
+
+def test_spike_clips_keep_their_logits_alone_and_elsewhere(spike):
+    """A clip's logits depend on neither the batch around it nor its place in it: the clips
+    not re-run equal, bit for bit, the same clip run alone and in the reversed batch (the
+    clean ones also the res15-speech batch's); the re-run clips equal a bf16x3 forward of
+    themselves."""
+    s, f = spike, spike.f
+    keep = np.nonzero(~s.reran)[0]
+    for i in keep:
+        alone = run(s.m, f["x"][i:i + 1])
+        assert s.m.honk_last_rerun == 0 and np.array_equal(alone[0], s.out[i]), i
+    back = run(s.m, np.ascontiguousarray(f["x"][::-1]))[::-1]
+    assert s.m.honk_last_rerun == s.rerun
+    assert np.array_equal(back[keep], s.out[keep])
+    clean = np.nonzero(f["kind"] == 0)[0]
+    assert np.array_equal(s.out[clean], s.clean[f["base"][clean]])
+    m3 = module(f["cfg"], f["params"], f["model"], "bf16x3")
+    m3.honk_reroute = False
+    np.testing.assert_allclose(s.out[s.reran], run(m3, f["x"][s.reran]), rtol=0, atol=1e-3)
+
+
+def test_spike_clips_raw_f16x2_stay_finite(spike):
+    """HONK_F16X2_RERUN=0, the kernels alone: finite on every clip (the clip scale holds fp16's
+    range at a spike of 3e4); each clip's error is printed, not bounded -- the admission is
+    what answers for the clips past the bar."""
+    s = spike
+    _spike_table(s, s.raw_err, "raw f16x2")
+    assert np.isfinite(s.raw).all()
+
+
+def test_spike_clips_on_the_ordered_entry(spike):
+    from test_gpu_ordered import ordered
+    s = spike
+    out, count = ordered(s.m, s.f["x"])
+    assert s.m.honk_last_precision == "f16x2"
+    assert count == s.rerun and np.array_equal(out, s.out)

@@ -5,8 +5,15 @@
 * honk_res_select_precision's policy table (host-only: the library loads without a GPU);
 * the numerics record's definitions (scale, range, rho), restated in numpy, against
   which the GPU test (test_gpu_range.py) checks the device's pack;
-* the default precision's sources (config key, HONK_PRECISION, "auto")."""
+* the default precision's sources (config key, HONK_PRECISION, "auto");
+* the single-spike fixture (range_res15-spike: one loud entry or frame in a speech-scale
+  clip) holds the three classes the GPU test asks about -- inside the admission's |z| <= 8
+  with a lowered clip scale, beyond it, and clean -- and the clip-scale-aware rounding
+  simulation (oracle/res_round_sim.py) that predicts its f16x2 errors."""
 import ctypes
+import functools
+import os
+import re
 
 import numpy as np
 import pytest
@@ -14,7 +21,8 @@ import pytest
 from honk_amd import _native
 from honk_amd import model as hm
 from oracle import ref_numpy as orc
-from golden_util import load_fixture, load_range_fixture, range_fixture_names, ref_configs
+from oracle import res_round_sim as sim
+from golden_util import GOLDEN, load_fixture, load_range_fixture, range_fixture_names, ref_configs
 
 FP16_MAX = 65504.0
 
@@ -133,3 +141,100 @@ def test_default_precision_sources(monkeypatch):
     cfg["honk_precision"] = "bf16x3"   # an optional key the reference's _configs do not hold
     assert hm.SpeechResModel(cfg).honk_precision == "bf16x3"
     assert "honk_precision" not in hm.find_config("res15")
+
+
+# ---- range_res15-spike: one loud entry / frame in a speech-scale clip ----------------------
+def _header_constant(name):
+    """An integer #define of include/honk_hip.h."""
+    with open(os.path.join(os.path.dirname(GOLDEN), "..", "include", "honk_hip.h")) as f:
+        return int(re.search(rf"^#define {name} (-?\d+)\s", f.read(), re.M).group(1))
+
+
+Z_MAX = 8      # HONK_F16X2_Z_MAX
+DROP_MAX = 4   # HONK_F16X2_DROP_MAX
+# the binades clip_scale_kernel lowers the clip's scale by, per largest |entry| of the clip
+# (bound / M = |amp| * 2.2762 / 95.678 < 2^ex; a clean clip's c0 reaches about -148: 2)
+SPIKE_DROP = {0.0: 2, 30.0: 2, 100.0: 2, 300.0: 3, 500.0: 4, 650.0: 4, 1000.0: 5, 1500.0: 6, 2000.0: 6, 2500.0: 6, 3000.0: 7,
+              1e4: 8, 3e4: 10}
+
+
+@functools.lru_cache(maxsize=None)
+def spike_fixture():
+    """range_res15-spike with, per clip, the float64 oracle's logits and largest last-layer
+    BatchNorm'd channel mean |z| (the admission's statistic), clip_scale_kernel's scale and
+    the binades ex it lies below s_model, and the classes: beyond = |z| > 8 (all that the
+    last-layer statistic re-runs), rerun = beyond or ex > HONK_F16X2_DROP_MAX (what the
+    admission re-runs).  Computed once; the GPU tests share it, read-only."""
+    cfg, params, x, logits, model = load_range_fixture("res15-spike")
+    z = np.load(os.path.join(GOLDEN, "range_res15-spike.npz"), allow_pickle=False)
+    trace = []
+    ref = orc.res_forward(params, cfg, x, trace=trace)
+    zmax = np.abs(trace[-1].reshape(len(x), trace[-1].shape[1], -1).mean(axis=2)).max(axis=1)
+    rec = numerics_record(params, cfg)
+    scale, ex = sim.clip_scales(x, rec["scale"], rec["range"], rec["w0sum"])
+    d = dict(cfg=cfg, params=params, model=model, x=x, logits=logits, ref=ref, zmax=zmax, rec=rec, scale=scale, ex=ex,
+             kind=z["kind"], base=z["base"], amp=z["amp"], frame=z["frame"], beyond=zmax > Z_MAX,
+             rerun=(zmax > Z_MAX) | (ex > DROP_MAX))
+    for v in d.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return d
+
+
+def test_spike_fixture_holds_the_three_classes():
+    """Without a GPU: which clips the admission's last-layer statistic can see.  c0 of one
+    frame at -1000 .. -2500 and a +-30 frame stay a full unit inside |z| <= 8 (that statistic
+    does not re-run them) while their scales drop by up to 6 binades; -1e4, -3e4 and every
+    frame of +-1e3 or more lie a full unit beyond it (re-run).  (The kind-5 clip, -2500 on the
+    base clip with the largest |z|, and c0 = -3000 are inside / beyond by less: 7.65, 8.9.)
+    The scale-drop statistic (ex > HONK_F16X2_DROP_MAX) takes every clip from -1000 on."""
+    f = spike_fixture()
+    assert Z_MAX == _header_constant("HONK_F16X2_Z_MAX") and DROP_MAX == _header_constant("HONK_F16X2_DROP_MAX")
+    kind, amp, zmax, ex = f["kind"], f["amp"], f["zmax"], f["ex"]
+    assert 20 <= len(kind) <= 24 and set(kind) == {0, 1, 2, 3, 4, 5}
+    _, _, xs, ls, _ = load_range_fixture("res15-speech")
+    clean = kind == 0
+    assert clean.sum() == 2 and np.array_equal(f["x"][clean], xs[f["base"][clean]])
+    assert np.array_equal(f["logits"][clean], ls[f["base"][clean]])
+    for i in np.nonzero(~clean)[0]:   # one entry, or one frame, differs from the base clip
+        diff = f["x"][i] != xs[f["base"][i]]
+        assert diff.sum() == (40 if kind[i] == 4 else 1) and diff[f["frame"][i]].sum() == diff.sum(), i
+    for i in range(len(kind)):
+        print(f"clip {i:2d} kind {kind[i]} amp {amp[i]:8.0f} frame {f['frame'][i]:3d}: scale 2^-{ex[i]} below s_model, "
+              f"max|z| {zmax[i]:8.2f}, max|logit| {np.abs(f['ref'][i]).max():8.2f}")
+    inside = ((kind == 1) & (amp <= -1000) & (amp >= -2500)) | ((kind == 2) & (amp == -2000)) | (
+        (kind == 4) & (amp == 30)) | clean
+    beyond = ((kind <= 2) & (amp <= -1e4)) | ((kind == 4) & (amp >= 1e3))
+    assert inside.sum() == 9 and beyond.sum() == 7
+    assert (zmax[inside] <= Z_MAX - 1).all(), zmax[inside]
+    assert (zmax[beyond] >= Z_MAX + 1).all(), zmax[beyond]
+    assert (np.abs(zmax - Z_MAX) > 0.25).all()   # no clip sits on the threshold
+    assert f["beyond"].sum() == 10
+    # every clip's scale: s_model lowered by the binades its loudest entry asks for
+    want = np.array([SPIKE_DROP[abs(float(a))] for a in amp])
+    assert np.array_equal(ex, want), (ex, want)
+    assert np.array_equal(f["scale"], f["rec"]["scale"] * 0.5 ** want)
+    hole = inside & ~clean & (kind != 4)   # |z| <= 7 at a scale 2^-5 or 2^-6 below s_model
+    assert hole.sum() == 6 and (ex[hole] > DROP_MAX).all()
+    assert f["rerun"].sum() == 17 and not f["rerun"][(np.abs(amp) <= 650) & ~f["beyond"]].any()
+
+
+def test_spike_simulation_reproduces_the_clean_clips():
+    """The yardstick, not a bound on the kernel: the format-only float64 simulation of f16x2
+    with every stored tensor at the clip's scale, f16(t s) / s.  It leaves out the per-layer
+    weight exponents and the fp32 accumulation, so only the clean clips are asserted (within
+    5e-5 of the oracle); the spiked clips' simulated errors are printed beside the bar."""
+    f = spike_fixture()
+    out = sim.fwd(f["params"], f["cfg"], f["x"], sim.all_layers(f["cfg"], "f16"), scale=f["scale"])
+    err = np.abs(out - f["ref"]).max(axis=1)
+    bar = 1e-4 * np.maximum(1.0, np.abs(f["ref"]).max(axis=1))
+    for i in range(len(err)):
+        print(f"clip {i:2d} kind {f['kind'][i]} amp {f['amp'][i]:8.0f} 2^-{f['ex'][i]:<2d} max|z| {f['zmax'][i]:8.2f}: "
+              f"simulated f16x2 err {err[i]:.2e} = {err[i] / bar[i]:5.2f} bar")
+    assert np.isfinite(out).all()
+    assert (err[f["kind"] == 0] <= 5e-5).all()
+    # the scale matters to the simulation only through fp16's subnormals: at s_model every
+    # clean clip gives the same logits to 1e-6
+    unit = sim.fwd(f["params"], f["cfg"], f["x"][:2], sim.all_layers(f["cfg"], "f16"),
+                   scale=np.full(2, f["rec"]["scale"]))
+    assert np.abs(unit - out[:2]).max() <= 1e-5
