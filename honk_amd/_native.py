@@ -149,6 +149,10 @@ _PROTOS = {
     "honk_conv2d_dgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64] + [ctypes.c_int32] * 6),
     "honk_conv2d_dgrad_f32": (ctypes.c_int, [c_f32p] * 4 + [ctypes.c_int64] + [ctypes.c_int32] * 6
                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "honk_conv2d_train_plan": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int32] * 8
+                               + [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
+    "honk_maxpool2d_bwd_plan": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int32] * 5
+                                + [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
     "honk_conv_same_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64] + [ctypes.c_int32] * 4),
     "honk_conv_same_f32": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] + [ctypes.c_int32] * 5
                            + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
@@ -528,3 +532,36 @@ def conv3x3_plan(batch: int, c: int, h: int, w: int, dil: int, n_cus: int = 0):
             "wgrad": dict(family=CONV3X3_FAMILIES[out[8]], variant=chr(out[9]) if out[9] else None,
                           fixed=bool(out[10]), th=out[11], nband=out[12], grid=out[13]),
             "stats": bool(out[7]), "fold": bool(out[14])}
+
+
+# HONK_CONV2D_TRAIN_PLAN_* / HONK_MAXPOOL2D_BWD_PLAN_* of include/honk_hip.h, in order
+CONV2D_TRAIN_PLAN_FIELDS = ("M", "tn", "tk", "S", "mper", "dgrad_k", "dgrad_ktab", "dgrad_wf_aligned",
+                            "dgrad_grid_x", "dgrad_pad_blocks", "dgrad_pad_passes", "dgrad_m")
+MAXPOOL2D_BWD_PLAN_FIELDS = ("blocks", "passes")
+
+
+def conv2d_train_plan(batch: int, cin: int, h: int, w: int, cout: int, kh: int, kw: int, sh: int = 1, sw: int = 1):
+    """honk_conv2d_train_plan: how honk_conv2d_wgrad_f32 and (at stride 1; zeros otherwise)
+    honk_conv2d_dgrad_f32 run one conv shape, as a dict over CONV2D_TRAIN_PLAN_FIELDS (the
+    two flags as bool).  Host-only; a Linear of a [B, K] input with N outputs is
+    (B, K, 1, 1, N, 1, 1)."""
+    n = len(CONV2D_TRAIN_PLAN_FIELDS)
+    out = (ctypes.c_int64 * n)()
+    rc = load().honk_conv2d_train_plan(int(batch), int(cin), int(h), int(w), int(cout), int(kh), int(kw), int(sh),
+                                       int(sw), out, n)
+    if rc != n:
+        check(rc if rc < 0 else -1, "honk_conv2d_train_plan")
+    p = dict(zip(CONV2D_TRAIN_PLAN_FIELDS, (int(v) for v in out)))
+    p["dgrad_ktab"], p["dgrad_wf_aligned"] = bool(p["dgrad_ktab"]), bool(p["dgrad_wf_aligned"])
+    return p
+
+
+def maxpool2d_bwd_plan(batch: int, c: int, h: int, w: int, kh: int, kw: int):
+    """honk_maxpool2d_bwd_plan: dict(blocks, passes) of honk_maxpool2d_bwd_f32's grid-stride
+    loop.  Host-only."""
+    n = len(MAXPOOL2D_BWD_PLAN_FIELDS)
+    out = (ctypes.c_int64 * n)()
+    rc = load().honk_maxpool2d_bwd_plan(int(batch), int(c), int(h), int(w), int(kh), int(kw), out, n)
+    if rc != n:
+        check(rc if rc < 0 else -1, "honk_maxpool2d_bwd_plan")
+    return dict(zip(MAXPOOL2D_BWD_PLAN_FIELDS, (int(v) for v in out)))

@@ -15,7 +15,10 @@ gradient (``honk_conv2d_dgrad_f32``).  ``max_pool(x, pool)`` is ``nn.MaxPool2d``
 (stride = kernel) on ``honk_maxpool2d_f32`` / ``honk_maxpool2d_bwd_f32`` (the
 gradient goes to each window's first maximum, torch's index rule).  Dropout stays
 the module's own ``nn.Dropout`` (PyTorch's RNG stream and mask semantics, exactly
-what the reference runs on a device), and so do the Linear layers and the loss.
+what the reference runs on a device).  The Linear layers run natively too, through
+``honk_amd/head_train.py`` (``model.py::_torch_forward``): each is a 1x1 conv of a
+[B, in, 1, 1] map on the same forward and gradient kernels, dnn1's ReLU fused.
+``_native.conv2d_train_plan`` reports, without a GPU, how the two gradients run a shape.
 """
 from __future__ import annotations
 

@@ -959,9 +959,12 @@ static bool conv2f_applies(const honk_cnn_desc* d, int ph1, int pw1, int oh2, in
 }
 static size_t conv2f_frag_bytes(const honk_cnn_desc* d) { return (size_t)2 * d->c2_kh * d->c2_kw * 2 * 4 * 64 * 16; }
 
+// gridDim.x of conv_gemm_kernel: one workgroup per BM GEMM rows
+static int64_t gemm_grid_x(int64_t M) { return cdiv(M, BM); }
+
 static int launch_gemm(const GemmArgs& a, bool pool2, hipStream_t st, bool x3 = false) {
   if (a.M <= 0 || a.N <= 0) return HONK_OK;
-  const int64_t gm = cdiv(a.M, BM);
+  const int64_t gm = gemm_grid_x(a.M);
   if (gm > 0x7fffffff) return fail(HONK_ERR_ARG, "GEMM too large (M=%lld)", (long long)a.M);
   dim3 grid((unsigned)gm, (unsigned)cdiv(a.N, BN));
   TimedLaunch tl(st, 2.0 * (double)a.M * a.N * a.K);
@@ -1345,6 +1348,45 @@ static WgradPlanC wgrad_plan_c(int64_t batch, int cin, int h, int w, int cout, i
   return p;
 }
 
+// the launch of an elementwise grid-stride kernel of 256 threads (maxpool_bwd_kernel,
+// dgrad_pad_kernel): at most 65536 blocks, each thread going round `passes` times
+struct StridePlanC {
+  int64_t blocks, passes;
+};
+static StridePlanC stride_plan_c(int64_t total) {
+  StridePlanC p;
+  p.blocks = cdiv(total, 256) < 65536 ? cdiv(total, 256) : 65536;
+  p.passes = p.blocks > 0 ? cdiv(total, p.blocks * 256) : 0;
+  return p;
+}
+
+// honk_conv2d_dgrad_f32: the pad geometry, the workspace layout ([gp: g' zero-padded]
+// [wf: flipped weights]) and the launches (the call, the byte count and
+// honk_conv2d_train_plan read this one)
+struct DgradPlanC {
+  int oh, ow, php, pwp;  // g' dims; padded by (kh-1, kw-1) on every side
+  int64_t np, nw;        // floats of gp (wf starts there) and of wf
+  int64_t K, M;          // the GEMM's reduction cout*kh*kw and rows batch*h*w
+  StridePlanC pad;       // dgrad_pad_kernel
+  int64_t gx;            // conv_gemm_kernel gridDim.x
+  bool ktab;             // the GEMM's k->offset table in LDS (else computed per load)
+  bool wf_aligned;       // wf 16-byte aligned in a 256-byte-aligned workspace
+};
+static DgradPlanC dgrad_plan_c(int64_t batch, int cin, int h, int w, int cout, int kh, int kw) {
+  DgradPlanC p;
+  p.oh = h - kh + 1; p.ow = w - kw + 1;
+  p.php = p.oh + 2 * (kh - 1); p.pwp = p.ow + 2 * (kw - 1);
+  p.np = batch * cout * (int64_t)p.php * p.pwp;
+  p.nw = (int64_t)cout * cin * kh * kw;
+  p.K = (int64_t)cout * kh * kw;
+  p.M = batch * (int64_t)(p.php - kh + 1) * (p.pwp - kw + 1);
+  p.pad = stride_plan_c(p.np);
+  p.gx = gemm_grid_x(p.M);
+  p.ktab = p.K <= KTAB;
+  p.wf_aligned = (p.np * (int64_t)sizeof(float)) % 16 == 0;
+  return p;
+}
+
 
 // the weight / bias gradient launches (conv_wgrad_kernel + the fixed-order split sums)
 static int wgrad_launch(const float* in, const float* gy, const float* act, float* dw, float* db, int64_t batch,
@@ -1696,17 +1738,38 @@ int honk_maxpool2d_bwd_f32(const float* in, const float* gout, float* gin, int64
     return fail(HONK_ERR_ARG, "bad pool %dx%d on %dx%d", kh, kw, h, w);
   const int64_t total = batch * c * h * w;
   if (total == 0) return HONK_OK;
-  const int64_t blocks = cdiv(total, 256) < 65536 ? cdiv(total, 256) : 65536;
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, gout, gin,
+  const StridePlanC p = stride_plan_c(total);
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)p.blocks), dim3(256), 0, (hipStream_t)stream, in, gout, gin,
                      batch * c, h, w, kh, kw);
   HONK_LAUNCH_CHECK("maxpool_bwd_kernel");
   return HONK_OK;
 }
 
-static int conv_train_check(int64_t batch, int cin, int h, int w, int cout, int kh, int kw, int sh, int sw) {
+int honk_maxpool2d_bwd_plan(int64_t batch, int32_t c, int32_t h, int32_t w, int32_t kh, int32_t kw, int64_t* out,
+                            int32_t n_out) {
+  if (n_out < 0 || (n_out > 0 && !out)) return fail(HONK_ERR_ARG, "bad plan buffer");
+  if (batch < 0 || c < 1 || kh < 1 || kw < 1 || kh > h || kw > w)
+    return fail(HONK_ERR_ARG, "bad pool %dx%d on %dx%d", kh, kw, h, w);
+  const StridePlanC p = stride_plan_c(batch * c * h * w);
+  const int64_t v[HONK_MAXPOOL2D_BWD_PLAN_COUNT] = {p.blocks, p.passes};
+  for (int i = 0; i < n_out && i < HONK_MAXPOOL2D_BWD_PLAN_COUNT; ++i) out[i] = v[i];
+  return HONK_MAXPOOL2D_BWD_PLAN_COUNT;
+}
+
+// what honk_conv2d_wgrad_f32 takes; dgrad: what honk_conv2d_dgrad_f32 takes on top (the
+// GEMM's reduction is cout*kh*kw there)
+static int conv_train_check(int64_t batch, int cin, int h, int w, int cout, int kh, int kw, int sh, int sw,
+                            bool dgrad = false) {
   if (batch < 0 || cin < 1 || cout < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || kh > h || kw > w)
     return fail(HONK_ERR_ARG, "bad conv geometry (cin=%d %dx%d k=%dx%d s=%dx%d cout=%d)", cin, h, w, kh, kw, sh, sw,
                 cout);
+  // the kernels index k = (ci, kh, kw) in an int; conv_wgrad_kernel's gridDim.y is tk
+  const int64_t khw = (int64_t)kh * kw;
+  const int64_t kmax = dgrad ? 0x7fffffff : (int64_t)65535 * WG_BK;
+  const int chan = dgrad ? cout : cin;
+  if (khw > kmax || chan * khw > kmax)
+    return fail(HONK_ERR_UNSUPPORTED, "conv training: %s*kh*kw = %d*%d*%d too large (up to %lld)",
+                dgrad ? "cout" : "cin", chan, kh, kw, (long long)kmax);
   return HONK_OK;
 }
 
@@ -1715,6 +1778,35 @@ size_t honk_conv2d_wgrad_workspace_bytes(int64_t batch, int32_t cin, int32_t h, 
   if (batch < 1 || conv_train_check(batch, cin, h, w, cout, kh, kw, sh, sw) != HONK_OK) return 0;
   const WgradPlanC p = wgrad_plan_c(batch, cin, h, w, cout, kh, kw, sh, sw);
   return (size_t)p.S * ((size_t)cout * cin * kh * kw + cout) * sizeof(float);
+}
+
+int honk_conv2d_train_plan(int64_t batch, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t kh, int32_t kw,
+                           int32_t sh, int32_t sw, int64_t* out, int32_t n_out) {
+  if (n_out < 0 || (n_out > 0 && !out)) return fail(HONK_ERR_ARG, "bad plan buffer");
+  int rc = conv_train_check(batch, cin, h, w, cout, kh, kw, sh, sw);
+  if (rc) return rc;
+  if (batch < 1) return fail(HONK_ERR_ARG, "conv training plan: batch %lld", (long long)batch);
+  int64_t v[HONK_CONV2D_TRAIN_PLAN_COUNT] = {0};
+  const WgradPlanC p = wgrad_plan_c(batch, cin, h, w, cout, kh, kw, sh, sw);
+  v[HONK_CONV2D_TRAIN_PLAN_M] = p.M;
+  v[HONK_CONV2D_TRAIN_PLAN_TN] = p.tn;
+  v[HONK_CONV2D_TRAIN_PLAN_TK] = p.tk;
+  v[HONK_CONV2D_TRAIN_PLAN_S] = p.S;
+  v[HONK_CONV2D_TRAIN_PLAN_MPER] = p.mper;
+  if (sh == 1 && sw == 1) {
+    rc = conv_train_check(batch, cin, h, w, cout, kh, kw, 1, 1, true);
+    if (rc) return rc;
+    const DgradPlanC q = dgrad_plan_c(batch, cin, h, w, cout, kh, kw);
+    v[HONK_CONV2D_TRAIN_PLAN_DGRAD_K] = q.K;
+    v[HONK_CONV2D_TRAIN_PLAN_DGRAD_KTAB] = q.ktab;
+    v[HONK_CONV2D_TRAIN_PLAN_DGRAD_WF_ALIGNED] = q.wf_aligned;
+    v[HONK_CONV2D_TRAIN_PLAN_DGRAD_GRID_X] = q.gx;
+    v[HONK_CONV2D_TRAIN_PLAN_DGRAD_PAD_BLOCKS] = q.pad.blocks;
+    v[HONK_CONV2D_TRAIN_PLAN_DGRAD_PAD_PASSES] = q.pad.passes;
+    v[HONK_CONV2D_TRAIN_PLAN_DGRAD_M] = q.M;
+  }
+  for (int i = 0; i < n_out && i < HONK_CONV2D_TRAIN_PLAN_COUNT; ++i) out[i] = v[i];
+  return HONK_CONV2D_TRAIN_PLAN_COUNT;
 }
 
 int honk_conv2d_wgrad_f32(const float* in, const float* gy, const float* act, float* dw, float* db, int64_t batch,
@@ -1737,35 +1829,30 @@ int honk_conv2d_wgrad_f32(const float* in, const float* gy, const float* act, fl
 
 size_t honk_conv2d_dgrad_workspace_bytes(int64_t batch, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t kh,
                                          int32_t kw) {
-  if (batch < 1 || conv_train_check(batch, cin, h, w, cout, kh, kw, 1, 1) != HONK_OK) return 0;
-  const int64_t oh = h - kh + 1, ow = w - kw + 1;
-  const int64_t php = oh + 2 * (kh - 1), pwp = ow + 2 * (kw - 1);
-  return (size_t)(batch * cout * php * pwp + (int64_t)cout * cin * kh * kw) * sizeof(float);
+  if (batch < 1 || conv_train_check(batch, cin, h, w, cout, kh, kw, 1, 1, true) != HONK_OK) return 0;
+  const DgradPlanC p = dgrad_plan_c(batch, cin, h, w, cout, kh, kw);
+  return (size_t)(p.np + p.nw) * sizeof(float);
 }
 
 int honk_conv2d_dgrad_f32(const float* gy, const float* act, const float* w, float* dx, int64_t batch, int32_t cin,
                           int32_t h, int32_t w_, int32_t cout, int32_t kh, int32_t kw, void* workspace,
                           size_t ws_bytes, void* stream) {
-  int rc = conv_train_check(batch, cin, h, w_, cout, kh, kw, 1, 1);
+  int rc = conv_train_check(batch, cin, h, w_, cout, kh, kw, 1, 1, true);
   if (rc) return rc;
   if (!gy || !w || !dx) return fail(HONK_ERR_ARG, "null pointer argument");
   if (batch == 0) return HONK_OK;
   const size_t need = honk_conv2d_dgrad_workspace_bytes(batch, cin, h, w_, cout, kh, kw);
   if (!workspace || ws_bytes < need) return fail(HONK_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
-  const int oh = h - kh + 1, ow = w_ - kw + 1;
-  const int php = oh + 2 * (kh - 1), pwp = ow + 2 * (kw - 1);
+  const DgradPlanC p = dgrad_plan_c(batch, cin, h, w_, cout, kh, kw);
   float* gp = (float*)workspace;
-  float* wf = gp + batch * cout * (int64_t)php * pwp;
-  const int64_t np = batch * cout * (int64_t)php * pwp;
-  const int64_t blocks = cdiv(np, 256) < 65536 ? cdiv(np, 256) : 65536;
-  hipLaunchKernelGGL(dgrad_pad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, gy, act, gp, batch * cout, oh, ow,
-                     php, pwp, kh, kw);
+  float* wf = gp + p.np;
+  hipLaunchKernelGGL(dgrad_pad_kernel, dim3((unsigned)p.pad.blocks), dim3(256), 0, st, gy, act, gp, batch * cout,
+                     p.oh, p.ow, p.php, p.pwp, kh, kw);
   HONK_LAUNCH_CHECK("dgrad_pad_kernel");
-  const int64_t nw = (int64_t)cout * cin * kh * kw;
-  hipLaunchKernelGGL(flip_weights_kernel, dim3((unsigned)cdiv(nw, 256)), dim3(256), 0, st, w, wf, cout, cin, kh, kw);
+  hipLaunchKernelGGL(flip_weights_kernel, dim3((unsigned)cdiv(p.nw, 256)), dim3(256), 0, st, w, wf, cout, cin, kh, kw);
   HONK_LAUNCH_CHECK("flip_weights_kernel");
-  return conv(gp, wf, nullptr, dx, batch, cout, php, pwp, cin, kh, kw, 1, 1, 0, st);
+  return conv(gp, wf, nullptr, dx, batch, cout, p.php, p.pwp, cin, kh, kw, 1, 1, 0, st);
 }
 
 // ---- the res block conv for any channel count (model.py:94-98: 3x3, padding =

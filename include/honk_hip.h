@@ -427,6 +427,43 @@ size_t honk_conv2d_dgrad_workspace_bytes(int64_t batch, int32_t cin, int32_t h, 
 int honk_conv2d_dgrad_f32(const float* gy, const float* act, const float* w, float* dx, int64_t batch, int32_t cin,
                           int32_t h, int32_t w_, int32_t cout, int32_t kh, int32_t kw, void* workspace,
                           size_t workspace_bytes, void* stream);
+/*
+ * Host-only introspection (no launch, no device): how the two gradients above run one
+ * conv shape -- the values the launches themselves read.  Writes the first
+ * min(n_out, HONK_CONV2D_TRAIN_PLAN_COUNT) of the values below and returns
+ * HONK_CONV2D_TRAIN_PLAN_COUNT, or the HONK_ERR_* code the gradients refuse the shape
+ * with (batch < 1 is refused here: nothing is planned for it).  The weight gradient:
+ * M = batch*oh*ow reduction rows, a grid of (TN, TK, S) workgroups (64 out channels x 64
+ * (ci,kh,kw) columns x one split of MPER rows, a multiple of the 32-row stage; the last
+ * split takes what is left).  The input gradient (sh == sw == 1; zeros otherwise): the
+ * GEMM's reduction DGRAD_K = cout*kh*kw and rows DGRAD_M = batch*h*w, whether its
+ * k->offset table is in LDS (DGRAD_K <= 4096) or computed, whether the flipped weights
+ * (behind the padded g' in the workspace) are 16-byte aligned given a 256-byte-aligned
+ * workspace (else the GEMM reads them one float at a time), its gridDim.x, and the block
+ * count and passes per thread of the padding kernel's grid-stride loop.
+ */
+enum {
+  HONK_CONV2D_TRAIN_PLAN_M = 0,
+  HONK_CONV2D_TRAIN_PLAN_TN = 1,
+  HONK_CONV2D_TRAIN_PLAN_TK = 2,
+  HONK_CONV2D_TRAIN_PLAN_S = 3,
+  HONK_CONV2D_TRAIN_PLAN_MPER = 4,
+  HONK_CONV2D_TRAIN_PLAN_DGRAD_K = 5,
+  HONK_CONV2D_TRAIN_PLAN_DGRAD_KTAB = 6,
+  HONK_CONV2D_TRAIN_PLAN_DGRAD_WF_ALIGNED = 7,
+  HONK_CONV2D_TRAIN_PLAN_DGRAD_GRID_X = 8,
+  HONK_CONV2D_TRAIN_PLAN_DGRAD_PAD_BLOCKS = 9,
+  HONK_CONV2D_TRAIN_PLAN_DGRAD_PAD_PASSES = 10,
+  HONK_CONV2D_TRAIN_PLAN_DGRAD_M = 11,
+  HONK_CONV2D_TRAIN_PLAN_COUNT = 12
+};
+int honk_conv2d_train_plan(int64_t batch, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t kh, int32_t kw,
+                           int32_t sh, int32_t sw, int64_t* out, int32_t n_out);
+/* The same for honk_maxpool2d_bwd_f32 (a call of its own, so a query of its own): the block
+ * count and the passes per thread of its grid-stride loop over batch*c*h*w elements. */
+enum { HONK_MAXPOOL2D_BWD_PLAN_BLOCKS = 0, HONK_MAXPOOL2D_BWD_PLAN_PASSES = 1, HONK_MAXPOOL2D_BWD_PLAN_COUNT = 2 };
+int honk_maxpool2d_bwd_plan(int64_t batch, int32_t c, int32_t h, int32_t w, int32_t kh, int32_t kw, int64_t* out,
+                            int32_t n_out);
 
 /*
  * The res block conv for ANY channel count C (3x3, padding = dilation = dil, no bias,
